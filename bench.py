@@ -2,6 +2,8 @@
 """Throughput of the DemoVLP cross-modal hot path on MI355X: video-text pairs/s, fwd + bwd + optimizer step.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a torchrun environment: starts its own N ranks)
+    python bench.py --gpus N --steps K --warmup W --full   (also the roofline, tower breakdown, CPU baseline, exchange timings)
+    python bench.py ... --dump-outputs DIR                 (the last timed step's outputs as DIR/<name>.npy)
 
 A step = trainer/trainer_dist.py:144-171 on one synthetic batch already resident in HBM: ObjectRelation forward (region
 transformer + DistilBERT), sim_matrix, GlobalLocalLoss (NT-Xent-style global + region<->word local loss, focal gate
@@ -10,10 +12,16 @@ features + random captions, per-GPU batch 64, bf16 MFMA / fp32 accumulate, rando
 N > 1: pure data parallel (weak scaling), gradient all-reduce over RCCL overlapped with backward; per-rank local
 negatives exactly as the reference trains.
 
-Prints ONE JSON line (rank 0).  ``roofline`` is for the dominant kernel (the MFMA GEMM family): algorithmic flops of
-all its launches / their summed duration, measured with HIP events on the launch stream inside the timed region.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps (``ms_per_step``, ``value``), writes the
+outputs if asked and prints the line; everything below is measured only with ``--full``, after the timed region.
+``roofline`` is for the dominant kernel (the MFMA GEMM family): algorithmic flops of all its launches / their summed
+duration, measured with HIP events on the launch stream (an eager pass behind the graph-replayed timed region).
 ``cpu_baseline`` times the CPU oracle (oracle/restatement.py, a port proven equal to the reference by tests/golden) on
-the host cores, on a bounded sample.
+the host cores, on a bounded sample.  N > 1: ``grad_allreduce_ms_standalone`` and ``grad_exchange_pieces``.
+
+``--dump-outputs DIR``: what the last timed step handed its caller -- the three losses and, on a fixed seeded sample of
+DUMP_SAMPLE positions of the flat parameter arena, the updated fp32 master weights and the step's gradients -- as float32
+.npy files (rank 0).  The inputs and weights are seeded, so two builds run with the same arguments can be compared.
 """
 import argparse
 import json
@@ -30,6 +38,8 @@ if ROOT not in sys.path:
 PEAK_BF16_TFLOPS = 2500.0        # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
 PEAK_F32_TFLOPS = 157.3
 TRAFFIC_FILES = ("r6_final_gemm_hbm_traffic_pmc.json", "r5_final_gemm_hbm_traffic_pmc.json", "r4_final_gemm_hbm_traffic_pmc.json", "r3_final_gemm_hbm_traffic_pmc.json", "r2_final_gemm_hbm_traffic_pmc.json", "r1_final_gemm_hbm_traffic_pmc.json")
+DUMP_SAMPLE = 1 << 22            # arena positions in the --dump-outputs sample (2 x 16 MB of float32)
+DUMP_SEED = 2024
 
 
 def csrc_sha():
@@ -119,6 +129,21 @@ def cpu_baseline(F, R):
     return dict(value=round(max(v2, v16), 3), unit="pairs/s", cores=cores, kind="port", cpu=cpu_model_name(),
                 pairs_per_s_b2=round(v2, 3), pairs_per_s_b16=round(v16, 3),
                 sample=f"oracle.train_step (fwd+loss+bwd, fp32, torch CPU, {cores} threads) at F={F}, R={R}; {d2}; {d16}")
+
+
+def dump_outputs(out_dir, losses, arena):
+    """--dump-outputs: the last timed step's three losses and a seeded sample of the flat arena (updated fp32 master weights and
+    the step's gradients, at the same positions) as float32 .npy files; the positions depend only on DUMP_SEED and the arena size."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(("loss", "global_loss", "local_loss"), losses):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().reshape(1).cpu().numpy())
+    n = min(DUMP_SAMPLE, arena.total)
+    pos = np.sort(np.random.default_rng(DUMP_SEED).choice(arena.total, n, replace=False))
+    idx = torch.from_numpy(pos).to(arena.flat_p.device)
+    np.save(os.path.join(out_dir, "params_sample.npy"), arena.flat_p[idx].cpu().numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), arena.flat_g[idx].cpu().numpy())
 
 
 def spawn_ranks(n):
@@ -250,7 +275,14 @@ def main():
     ap.add_argument("--gather-negatives", action="store_true",
                     help="cross-GPU negatives: all-gather the embeddings for the contrastive losses (opt-in; the reference trains "
                          "with per-rank negatives, trainer/trainer_dist.py:148-165)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, after the timed region: GEMM roofline (per-launch event timing), "
+                         "object / text tower and loss breakdown, CPU baseline, N > 1 exchange timings (the --no-* switches above trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (losses, a seeded sample of the updated weights and gradients) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a.gpus))          # before anything initialises the GPU in this process
@@ -332,18 +364,19 @@ def main():
         torch.cuda.synchronize()
 
     def step():
+        """(loss, global loss, local loss) of one step."""
         if stepper is not None:
-            return stepper(data)[0]
-        return train_step(model, loss_fn, opt, data, reducer, gather_negatives=gather)[0]
+            return stepper(data)
+        return train_step(model, loss_fn, opt, data, reducer, gather_negatives=gather)
 
     if use_graph:
         a.warmup = max(a.warmup, 3)              # two eager steps + the capturing one must precede the timed region
-    loss = None
+    losses = None
     step1_loss = None
     for i in range(a.warmup):
-        loss = step()
+        losses = step()
         if i == 0:
-            step1_loss = float(loss.item())
+            step1_loss = float(losses[0].item())
     if stepper is not None and stepper.inputs is not None:
         # the batch lives in the graphs' input buffers from here on -- where RegionBatcher.to_device(out=stepper.inputs) puts the
         # selection kernel's output in a real run -- so a step carries no device-to-device copy of its input
@@ -354,21 +387,24 @@ def main():
         ins["object_mask"].copy_(data["object_mask"])
         data = ins
     sync()
-    timing_inline = not a.no_kernel_timing and not use_graph
+    kernel_timing = a.full and not a.no_kernel_timing
+    timing_inline = kernel_timing and not use_graph
     if timing_inline:
         model.parallel_towers = False                    # per-launch event timings need one stream
         ops.XATTN_ONE_STREAM = True                      # (per-call option of dvlp_xattn_fwd / _bwd: no process-global switch is flipped)
         ops.prof_enable(True)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = step()
+        losses = step()
     host_elapsed = time.perf_counter() - t0          # time for the host to ENQUEUE the steps (launch-bound if ~= elapsed)
     sync()
     elapsed = time.perf_counter() - t0
-    final_loss = float(loss.item())
+    final_loss = float(losses[0].item())
+    if a.dump_outputs and rank == 0:                 # before anything below steps the model further
+        dump_outputs(a.dump_outputs, losses, arena)
     my_elapsed = elapsed
     eager_ms = None
-    if not a.no_kernel_timing and use_graph:
+    if kernel_timing and use_graph:
         # per-launch HIP events cannot be recorded inside a captured graph: the GEMM family is timed over an equally long EAGER
         # region right behind the replayed one (same kernels, same shapes, same launch order, the stream they are launched on)
         model.parallel_towers = False                # one stream: per-launch event timings are only meaningful without concurrent kernels
@@ -383,14 +419,14 @@ def main():
         eager_ms = 1e3 * (time.perf_counter() - t1) / a.steps
     ops.XATTN_ONE_STREAM = False
     ops.prof_enable(False)
-    gemm_ms, gemm_flops, gemm_n = ops.prof_collect() if not a.no_kernel_timing else (0.0, 0.0, 0)
+    gemm_ms, gemm_flops, gemm_n = ops.prof_collect() if kernel_timing else (0.0, 0.0, 0)
 
     tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
 
-    # after the timed region: per-rank rates, a stand-alone all-reduce of the whole gradient arena, the object tower alone
+    # after the timed region: per-rank rates; with --full also a stand-alone all-reduce of the whole gradient arena, the towers alone
     per_rank = None
     allreduce_ms = None
     if world > 1 or force_dist:
@@ -398,6 +434,7 @@ def main():
         rates[rank] = B * a.steps / my_elapsed
         dist.all_reduce(rates)
         per_rank = [round(float(x), 1) for x in rates.tolist()]
+    if (world > 1 or force_dist) and a.full:
         for it in range(4):
             if it == 1:
                 sync()
@@ -406,7 +443,7 @@ def main():
         sync()
         allreduce_ms = round(1e3 * (time.perf_counter() - t1) / 3, 3)
     exchange = None
-    if (world > 1 or force_dist) and use_graph and getattr(stepper, "collective", False):
+    if (world > 1 or force_dist) and a.full and use_graph and getattr(stepper, "collective", False):
         # per-piece exchange times: three more steps with HIP events around every piece's collectives on the communication stream (outside the
         # timed region: the events make the host wait for each piece's handles)
         stepper.time_exchange = True
@@ -421,7 +458,7 @@ def main():
             exchange.append({"piece": k, "mb": round(mine[0][1] / 2 ** 20, 1) if mine else 0.0,
                              "ms": round(sum(t for t, _ in mine) / len(mine), 3) if mine else 0.0})
     obj_s, obj_mode, text_s, loss_s = None, None, None, None
-    if not a.no_object_tower:
+    if a.full and not a.no_object_tower:
         obj_s, obj_mode = time_object_tower(model, data, max(3, min(a.steps, 10)), sync, graph=use_graph)
         try:          # the step's other two terms, timed the same way (breakdown only: a failure here must not cost the bench line)
             text_s = time_object_tower(model, data, max(3, min(a.steps, 10)), sync, graph=use_graph, part="text")[0]
@@ -456,7 +493,8 @@ def main():
             out["INVALID_timing_only_ablation"] = "DVLP_ABLATE_LN_FWD=1: forward LayerNorm passes skipped (results wrong): an upper bound for LayerNorm fusion, not a throughput figure"
         if per_rank is not None:
             out["per_rank_pairs_per_s"] = per_rank
-            out["grad_allreduce_ms_standalone"] = allreduce_ms
+            if allreduce_ms is not None:
+                out["grad_allreduce_ms_standalone"] = allreduce_ms
             out["grad_allreduce_bytes"] = int(arena.flat_g.numel() * 4)
             if exchange is not None:
                 out["grad_exchange_pieces"] = exchange          # time each piece's collectives occupy the communication stream (all but the last run beside the next graph)
@@ -516,7 +554,7 @@ def main():
         if not gemm_n and obj_s is not None:        # (--no-kernel-timing: no roofline object; the object tower's figure stands alone)
             out["object_transformer"] = {"ms": round(1e3 * obj_s, 3), "launch_mode": obj_mode, "tflops": round(B * fpp_obj / obj_s / 1e12, 2),
                                          "frac": round(B * fpp_obj / obj_s / 1e12 / peak, 4)}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(F, R)
         print(json.dumps(out), flush=True)
     if world > 1 or force_dist:

@@ -121,6 +121,7 @@ ROWS = {
     "test_soak_replayed_steps_hold_memory_and_learn": "A14 d",
     "test_qa_model_vs_reference_golden": "f4",
     "test_bench_launches_its_own_ranks": "e d",
+    "test_bench_plain_run_is_lean_and_dumps_reproducible_outputs": "d",
     # ---- tests/test_gpu_round3.py
     "test_two_rank_graphed_step_matches_hand_averaged_gradients": "A13 e A14",
     "test_gather_negatives_two_ranks_on_device_vs_oracle": "A12 e A9 A11",

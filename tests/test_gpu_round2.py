@@ -376,7 +376,7 @@ def test_bench_rccl_path_in_a_one_rank_group(graph, gather):
     env = dict(os.environ, DVLP_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     # (the graph variant also carries its buckets as bf16 -- GraphedTrainStep(grad_dtype='bfloat16'): cast, RCCL sum in bf16, cast back)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline",
            "--graph", str(graph)] + (["--gather-negatives"] if gather else []) + (["--grad-dtype", "bf16"] if graph else [])
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     if r.returncode != 0:                   # one retry on a fresh port: process-group bring-up on a cold box is the only part not under our control
@@ -799,9 +799,41 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["DVLP_BENCH_ONE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--no-cpu-baseline", "--no-object-tower"], env=env, capture_output=True, text=True, timeout=1200)
+                        "--full", "--no-cpu-baseline", "--no-object-tower"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 8 and out["config"]["parallelism"] == "dp2"
     assert len(out["per_rank_pairs_per_s"]) == 2 and all(x > 0 for x in out["per_rank_pairs_per_s"])
     assert out["value"] > 0 and out["grad_allreduce_ms_standalone"] > 0 and np.isfinite(out["config"]["final_loss"])
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the JSON line carries the headline fields and
+    none of the --full measurements, and DIR holds the last timed step's outputs (three losses, a seeded sample of the updated weights
+    and of the gradients) as float32 .npy files within 64 MB.  A second process with the same arguments dumps the same outputs."""
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["unit"] == "pairs/s" and out["higher_is_better"] is True and out["dtype"] == "bf16" and out["steps"] == 3
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and abs(out["value"] - 4 * 1e3 / out["ms_per_step"]) < 0.01 * out["value"]
+        assert not {"roofline", "object_transformer", "cpu_baseline"} & set(out), sorted(out)
+        names = sorted(os.listdir(d))
+        assert names == sorted(n + ".npy" for n in ("loss", "global_loss", "local_loss", "params_sample", "grads_sample")), names
+        assert sum(os.path.getsize(d / n) for n in names) <= 64 << 20
+        arr = {n[:-4]: np.load(d / n) for n in names}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in arr.values())
+        assert abs(float(arr["loss"][0]) - out["config"]["final_loss"]) < 1e-3 * max(1.0, abs(out["config"]["final_loss"]))
+        assert arr["params_sample"].shape == arr["grads_sample"].shape and np.abs(arr["grads_sample"]).max() > 0
+        dumps.append(arr)
+    a, b = dumps
+    for n in ("loss", "global_loss", "local_loss"):
+        assert abs(float(a[n][0]) - float(b[n][0])) <= 1e-4 * max(1.0, abs(float(a[n][0]))), (n, a[n], b[n])
+    print("\nrun-to-run: params max |diff| %.3e, grads max |diff| %.3e of max |g|" % (
+        np.abs(a["params_sample"] - b["params_sample"]).max(),
+        np.abs(a["grads_sample"] - b["grads_sample"]).max() / np.abs(a["grads_sample"]).max()))
+    assert np.abs(a["params_sample"] - b["params_sample"]).max() <= 1e-4
+    assert np.abs(a["grads_sample"] - b["grads_sample"]).max() <= 1e-2 * np.abs(a["grads_sample"]).max()

@@ -6,7 +6,7 @@ i=0
 for rep in 1 2; do
   j=0
   for v in "$@"; do
-    python bench.py --no-cpu-baseline $v 2>"$out/err_${j}_$rep.txt" | tail -1 > "$out/bench_${j}_$rep.json"
+    python bench.py --full --no-cpu-baseline $v 2>"$out/err_${j}_$rep.txt" | tail -1 > "$out/bench_${j}_$rep.json"
     python - "$out/bench_${j}_$rep.json" "$v" <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 N=${1:-3}
 for i in $(seq 1 "$N"); do
-    python bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('run $i: %.3f ms/step  %.1f pairs/s  object tower %.2f ms  text tower %.2f ms  loss heads %.2f ms' % (

@@ -1,6 +1,7 @@
 #!/bin/bash
 # kernel resource usage of one csrc file:  tools/kres.sh attention.hip [grep pattern]
-cd /tmp && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Rpass-analysis=kernel-resource-usage -c /root/repo/demovlp_amd/csrc/$1 -o /tmp/kres_$$.o 2>&1 | python3 -c "
+root=$(cd "$(dirname "$0")/.." && pwd)
+cd /tmp && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Rpass-analysis=kernel-resource-usage -c "$root/demovlp_amd/csrc/$1" -o /tmp/kres_$$.o 2>&1 | python3 -c "
 import sys, re
 cur = None
 rows = []

@@ -71,7 +71,7 @@ if fc and wc:
     (fs, fn), (ws, wn) = fe["gemm_bf16"], wr["gemm_bf16"]
     # FETCH_SIZE / WRITE_SIZE count KiB; gfx950 reports half the bytes of wide coalesced reads -> reads are doubled
     traffic = (2.0 * fs / fn + ws / wn) * 1024.0
-    out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python3 bench.py --steps 2 "
+    out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python3 bench.py --full --steps 2 "
                      "--warmup 1 --no-kernel-timing --no-cpu-baseline, MI355X (tools/profile_round.sh)",
            "note": "KiB of L2<->fabric traffic (Infinity-Cache hits included); reads doubled per MI355X_MICROARCH.md (HBM section); the split-K "
                    "slab reductions are charged to the GEMM launch they belong to",
@@ -95,7 +95,7 @@ if mc:
             if r["Counter_Name"] == "GRBM_GUI_ACTIVE":
                 cnt[f] += 1
     out = {"source": "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES "
-                     "SQ_WAIT_ANY SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE -- python3 bench.py --steps 2 --warmup 1 (tools/profile_round.sh)",
+                     "SQ_WAIT_ANY SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE -- python3 bench.py --full --steps 2 --warmup 1 (tools/profile_round.sh)",
            "note": "mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 x 256 CUs x 4 SIMDs): the gfx94x MfmaUtil formula with GRBM_GUI_ACTIVE, which "
                    "rocprofv3 reports summed over the 8 XCDs, brought back to one clock (cross-check: p8 kernels 0.30 busy ~ 750 TFLOP/s of 2500; ROCm 7.2 ships no gfx950 "
                    "derived-counter section); lds_conflict = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE; parked = SQ_WAIT_ANY / SQ_WAVE_CYCLES "
