@@ -48,6 +48,8 @@ bool dvlp_xfused_ok(int64_t G, int64_t W);
 int64_t dvlp_xfused_workspace_bytes(int64_t Bi, int64_t Bj, int64_t G, int64_t W);
 int dvlp_xfused_fwd(int64_t Bi, int64_t Bj, int64_t G, int64_t W, const void* Craw, const void* Qraw, const float* mimg, const float* mcap,
                     float lam, int gate, float* scores, void* workspace, hipStream_t st);
+int dvlp_xfused_pairs_fwd(int64_t Bi, int64_t Bj, int64_t K, int64_t G, int64_t W, const void* Craw, const void* Qraw, const float* mimg,
+                          const float* mcap, const int* cand, float lam, int gate, float* scores, void* workspace, hipStream_t st);
 static int g_fused = 1;          // 1 (default): use the fused kernels where they apply; 0: always the multi-kernel path (A/B, tests)
 DVLP_DEV_API int dvlp_dev_xattn_fused_mode(int mode) { g_fused = mode; return DVLP_OK; }
 static bool x_fused(int dtype, int64_t G, int64_t W, int bwd) {
@@ -1458,6 +1460,91 @@ extern "C" int dvlp_xattn_fwd(int dtype, int64_t Bi, int64_t Bj, int64_t G, int6
     ca.nc = L.gram ? (const float*)(ws + L.off_nc) : nullptr;
     DT(xcos_fwd_kernel, dim3((unsigned)Bj, (unsigned)Bi), b256, 0, st, ca);
     return dvlp_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// pair list: scores[i][k] = local similarity of video i and caption cand[i K + k] (NULL cand: i K + k), forward only
+// (multiple-choice evaluation, trainer/trainer_dist.py:820-829; re-ranking of a global-similarity shortlist)
+// ------------------------------------------------------------------------------------------------------------------
+// outside the fused kernel's range (fp32, G > 288, W > 112): per video, its K captions are gathered into a contiguous pool [K][W][d]
+// (+ masks [K][W]) and the multi-kernel path scores that 1 x K grid.  Workspace: gathered pool, its masks, the 1 x K grid's workspace.
+struct XPairsLayout { int64_t off_qg, off_mg, off_sub, total; };
+static XPairsLayout xpairs_layout(int dtype, int64_t K, int64_t G, int64_t W) {
+    XPairsLayout P{};
+    const int64_t es = dtype == DVLP_F32 ? 4 : 2;
+    P.off_qg = 0;
+    P.off_mg = rup(K * W * XD * es, 256);
+    P.off_sub = P.off_mg + rup(K * W * 4, 256);
+    P.total = P.off_sub + xlayout(dtype, 1, K, G, W, 0).total;
+    return P;
+}
+
+// 16-byte pieces of the K rows [W][d] of video i's captions; an index outside [0, Bj) gathers zeros (its score is set to NaN afterwards)
+__global__ __launch_bounds__(256) void xpairs_gather_kernel(int64_t i, int K, int Bj, int W, int es, const int* __restrict__ cand,
+                                                            const char* __restrict__ Qraw, const float* __restrict__ mcap, char* __restrict__ Qg,
+                                                            float* __restrict__ mg) {
+    const int64_t per = (int64_t)XD * es / 16;
+    const int64_t n = (int64_t)K * W * per;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = t / per, c = t % per;
+        const int k = (int)(row / W), w = (int)(row % W);
+        const int64_t o = i * K + k;
+        const int64_t j = cand ? (int64_t)cand[o] : o;
+        const bool ok = j >= 0 && j < Bj;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (ok) v = ((const uint4*)(Qraw + (j * W + w) * XD * es))[c];
+        ((uint4*)(Qg + row * XD * es))[c] = v;
+        if (c == 0) mg[row] = ok ? mcap[j * W + w] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void xpairs_invalid_kernel(int64_t n, int Bj, const int* __restrict__ cand, float* __restrict__ scores) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n && (cand[t] < 0 || cand[t] >= Bj)) scores[t] = __builtin_nanf("");
+}
+
+extern "C" int64_t dvlp_xattn_pairs_workspace_bytes(int dtype, int64_t Bi, int64_t Bj, int64_t K, int64_t G, int64_t W) {
+    if (dtype != DVLP_F32 && dtype != DVLP_BF16) return DVLP_ERR_DTYPE;
+    if (Bi <= 0 || Bj <= 0 || K <= 0 || G <= 0 || W <= 0 || W > 32 * XMAX_NKW) return DVLP_ERR_SHAPE;
+    if (x_fused(dtype, G, W, 0)) return dvlp_xfused_workspace_bytes(Bi, Bj, G, W);
+    return xpairs_layout(dtype, K, G, W).total;
+}
+
+extern "C" int dvlp_xattn_pairs_fwd(int dtype, int64_t Bi, int64_t Bj, int64_t K, int64_t G, int64_t W, int64_t d, const void* Craw,
+                                    const void* Qraw, const float* mimg, const float* mcap, const int* cand, float lam, int gate, float* scores,
+                                    void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != XD || Bi <= 0 || Bj <= 0 || K <= 0 || G <= 0 || W <= 0 || W > 32 * XMAX_NKW) return DVLP_ERR_SHAPE;
+    if (Bi > 65535 || K > 65535 || Bi * K > INT32_MAX || (!cand && Bj < Bi * K)) return DVLP_ERR_SHAPE;
+    if (!Craw || !Qraw || !mimg || !mcap || !scores || !workspace) return DVLP_ERR_SHAPE;
+    if (dtype != DVLP_F32 && dtype != DVLP_BF16) return DVLP_ERR_DTYPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (x_fused(dtype, G, W, 0)) {
+        dvlp_xfused_pairs_fwd(Bi, Bj, K, G, W, Craw, Qraw, mimg, mcap, cand, lam, gate & 1, scores, workspace, st);
+        return dvlp_launch_status();
+    }
+    const XPairsLayout P = xpairs_layout(dtype, K, G, W);
+    const int64_t es = dtype == DVLP_F32 ? 4 : 2;
+    char* ws = (char*)workspace;
+    char* qg = ws + P.off_qg;
+    float* mg = (float*)(ws + P.off_mg);
+    const int64_t pieces = K * W * XD * es / 16;
+    const unsigned nblk = (unsigned)(cdiv(pieces, 256) < 1024 ? cdiv(pieces, 256) : 1024);
+    for (int64_t i = 0; i < Bi; ++i) {
+        dvlp_clear_status();
+        hipLaunchKernelGGL(xpairs_gather_kernel, dim3(nblk), dim3(256), 0, st, i, (int)K, (int)Bj, (int)W, (int)es, cand, (const char*)Qraw, mcap, qg, mg);
+        int rc = dvlp_launch_status();
+        if (rc != DVLP_OK) return rc;
+        rc = dvlp_xattn_fwd(dtype, 1, K, G, W, d, (const char*)Craw + i * G * XD * es, qg, mimg + i * G, mg, lam, gate, scores + i * K,
+                            ws + P.off_sub, 0, stream);
+        if (rc != DVLP_OK) return rc;
+    }
+    if (cand) {
+        dvlp_clear_status();
+        hipLaunchKernelGGL(xpairs_invalid_kernel, dim3((unsigned)cdiv(Bi * K, 256)), dim3(256), 0, st, Bi * K, (int)Bj, cand, scores);
+        return dvlp_launch_status();
+    }
+    return DVLP_OK;
 }
 
 // workspace must be the one dvlp_xattn_fwd(..., bwd=1) filled.  Outputs: dC [Bi][G][d], dQ [Bj][W][d] (compute dtype).

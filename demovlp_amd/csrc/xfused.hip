@@ -29,8 +29,9 @@ struct FusedArgs {
     const bf16 *chat, *chatT, *qhat, *qhatT;   // [Bi][Gr][256], [Bi][256][Gk], [Bj][Wp][256], [Bj][256][Wk]
     const float *nc, *nq;                      // |C_raw| [Bi][G], |Q_raw| [Bj][W]
     const float *mimg, *mcap;                  // additive masks [Bi][G], [Bj][W]
-    float* scores;                             // [Bi][Bj]
-    int Bi, Bj, G, W, Gr, Gk, Wp, Wk;
+    float* scores;                             // [Bi][Bj]; pair form: [Bi][K]
+    const int* cand;                           // pair form: caption of pair (i, k) = cand[i K + k] (NULL: i K + k)
+    int Bi, Bj, G, W, Gr, Gk, Wp, Wk, K;
     float lam;
     int gate;
     int stop;                                  // TIMING-ONLY ablation: stop after phase n (0 = run everything)
@@ -344,19 +345,21 @@ __device__ __forceinline__ void pair_forward(const FusedArgs& a, char* smem, int
     }
 }
 
-__global__ __launch_bounds__(512) void xf_fwd_kernel(FusedArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// The score of one (video i, caption j) pair -> *out: the whole forward of both launch shapes below (full grid, pair list), so that a
+// pair's arithmetic -- and its result, bit for bit -- does not depend on which of them computed it.
+__device__ __forceinline__ void xf_pair_score(const FusedArgs& a, char* smem, int i, int j, float* out) {
     const int tid = threadIdx.x, lane = tid & 63, lq = lane >> 4, lc = lane & 15;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = blockIdx.x, i = blockIdx.y;
     const int nbg = a.Gr >> 4, nwb = a.Wp >> 4;
     const FLds L = flds(a.Gr, a.Gk, a.Wp, a.Wk);
     float *dotg = (float*)(smem + L.dotg), *dotw = (float*)(smem + L.dotw), *nw1 = (float*)(smem + L.nw1), *nw2 = (float*)(smem + L.nw2);
     const bf16* P1s = (const bf16*)(smem + L.p1);
     const bf16* P2s = (const bf16*)(smem + L.p2);
     const int p1s = a.Gk + 8, p2s = a.Wk + 8;
-    for (int t = tid; t < 112; t += blockDim.x) nw1[t] = 0.f;
-    for (int t = tid; t < 384; t += blockDim.x) nw2[t] = 0.f;
+    // per-wave partials of |wc_w|^2 [8][112] (the exchange rows xa, dead once P1' / P2' are published) and of |wc2_g|^2 [8][p1s] (over P1',
+    // dead once every wave is past the wc product): summed in wave order below, so the result does not depend on which wave finished first
+    float* nw1p = (float*)(smem + L.xa);
+    float* nw2p = (float*)(smem + L.p1);
     {
         PairRegs R;
         pair_forward(a, smem, i, j, R);
@@ -381,7 +384,7 @@ __global__ __launch_bounds__(512) void xf_fwd_kernel(FusedArgs a) {
         }
     }
     __syncthreads();
-    if (a.stop >= 1 && a.stop <= 4) { if (tid == 0) a.scores[(int64_t)i * a.Bj + j] = dotg[0] + dotw[0]; return; }
+    if (a.stop >= 1 && a.stop <= 4) { if (tid == 0) *out = dotg[0] + dotw[0]; return; }
 
     // ---- |wc_w|^2: wc^T [d][w] = C^^T [d][g] P1'^T; wave wid owns channels 32 wid .. 32 wid + 31
     {
@@ -411,9 +414,10 @@ __global__ __launch_bounds__(512) void xf_fwd_kernel(FusedArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) q += acc[db][nb][r] * acc[db][nb][r];
             q = col4_sum(q);
-            if (nb < nwb && lq == 0) atomicAdd(&nw1[nb * 16 + lc], q);
+            if (nb < nwb && lq == 0) nw1p[wid * 112 + nb * 16 + lc] = q;
         }
     }
+    __syncthreads();                                       // every wave is done reading P1': its space takes the |wc2|^2 partials
     // ---- |wc2_g|^2: wc2^T [d][g] = Q^^T [d][w] P2'^T, two region blocks per iteration (independent accumulator chains)
     if (a.stop != 5) {
         for (int gb = 0; gb < nbg; gb += 2) {
@@ -432,8 +436,23 @@ __global__ __launch_bounds__(512) void xf_fwd_kernel(FusedArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) { q0 += c00[r] * c00[r] + c01[r] * c01[r]; q1 += c10[r] * c10[r] + c11[r] * c11[r]; }
             q0 = col4_sum(q0); q1 = col4_sum(q1);
-            if (lq == 0) { atomicAdd(&nw2[gb * 16 + lc], q0); if (gb + 1 < nbg) atomicAdd(&nw2[gb1 * 16 + lc], q1); }
+            if (lq == 0) { nw2p[wid * p1s + gb * 16 + lc] = q0; if (gb + 1 < nbg) nw2p[wid * p1s + gb1 * 16 + lc] = q1; }
         }
+    }
+    __syncthreads();
+    for (int t = tid; t < a.Wp; t += blockDim.x) {
+        float q = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) q += nw1p[w * 112 + t];
+        nw1[t] = q;
+    }
+    for (int t = tid; t < a.Gr; t += blockDim.x) {
+        float q = 0.f;
+        if (a.stop != 5) {
+#pragma unroll
+            for (int w = 0; w < 8; ++w) q += nw2p[w * p1s + t];
+        }
+        nw2[t] = q;
     }
     __syncthreads();
     // ---- cosines (loss.py:286-291, 317-327): means over ALL W words / G regions (padded ones included, as the reference)
@@ -455,8 +474,28 @@ __global__ __launch_bounds__(512) void xf_fwd_kernel(FusedArgs a) {
     if (tid == 0) {
         float t = 0.f;
         for (int w = 0; w < 8; ++w) t += red[w];
-        a.scores[(int64_t)i * a.Bj + j] = t;
+        *out = t;
     }
+}
+
+// full grid: workgroup (j, i) -> scores[i][j]
+__global__ __launch_bounds__(512) void xf_fwd_kernel(FusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int j = blockIdx.x, i = blockIdx.y;
+    xf_pair_score(a, smem, i, j, a.scores + (int64_t)i * a.Bj + j);
+}
+
+// pair list: workgroup (k, i) -> scores[i][k], caption cand[i K + k]; an index outside [0, Bj) reads nothing and scores NaN
+__global__ __launch_bounds__(512) void xf_pairs_fwd_kernel(FusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int i = blockIdx.y;
+    const int64_t o = (int64_t)i * a.K + blockIdx.x;
+    const int j = a.cand ? a.cand[o] : (int)o;
+    if (j < 0 || j >= a.Bj) {
+        if (threadIdx.x == 0) a.scores[o] = __builtin_nanf("");
+        return;
+    }
+    xf_pair_score(a, smem, i, j, a.scores + o);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -487,8 +526,9 @@ bool dvlp_xfused_ok(int64_t G, int64_t W) {
 }
 int64_t dvlp_xfused_workspace_bytes(int64_t Bi, int64_t Bj, int64_t G, int64_t W) { return fused_layout(Bi, Bj, G, W).total; }
 
-int dvlp_xfused_fwd(int64_t Bi, int64_t Bj, int64_t G, int64_t W, const void* Craw, const void* Qraw, const float* mimg, const float* mcap,
-                    float lam, int gate, float* scores, void* workspace, hipStream_t st) {
+// prep of the Bi videos and the Bj captions into the workspace; the kernel arguments of the pair kernels
+static FusedArgs xf_prep(int64_t Bi, int64_t Bj, int64_t G, int64_t W, const void* Craw, const void* Qraw, const float* mimg, const float* mcap,
+                         float lam, int gate, float* scores, void* workspace, hipStream_t st) {
     const FusedLayout F = fused_layout(Bi, Bj, G, W);
     char* ws = (char*)workspace;
     FusedArgs a{};
@@ -503,9 +543,27 @@ int dvlp_xfused_fwd(int64_t Bi, int64_t Bj, int64_t G, int64_t W, const void* Cr
                        (bf16*)(ws + F.off_chat), (bf16*)(ws + F.off_chatT), (float*)(ws + F.off_nc));
     hipLaunchKernelGGL(xf_prep_kernel, dim3((unsigned)cdiv(Bj * rq, 4)), dim3(256), 0, st, (int)Bj, (int)W, (int)F.Wp, (int)F.Wk, (const bf16*)Qraw,
                        (bf16*)(ws + F.off_qhat), (bf16*)(ws + F.off_qhatT), (float*)(ws + F.off_nq));
+    return a;
+}
+
+int dvlp_xfused_fwd(int64_t Bi, int64_t Bj, int64_t G, int64_t W, const void* Craw, const void* Qraw, const float* mimg, const float* mcap,
+                    float lam, int gate, float* scores, void* workspace, hipStream_t st) {
+    const FusedArgs a = xf_prep(Bi, Bj, G, W, Craw, Qraw, mimg, mcap, lam, gate, scores, workspace, st);
     const FLds L = flds(a.Gr, a.Gk, a.Wp, a.Wk);
     { static bool once = false; if (!once) { once = true;
         (void)hipFuncSetAttribute((const void*)xf_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
     hipLaunchKernelGGL(xf_fwd_kernel, dim3((unsigned)Bj, (unsigned)Bi), dim3(512), (size_t)L.total, st, a);
+    return 0;
+}
+
+// pair list (dvlp_xattn_pairs_fwd): the same prep over the Bi videos and the Bj pool captions, then one workgroup per (i, k)
+int dvlp_xfused_pairs_fwd(int64_t Bi, int64_t Bj, int64_t K, int64_t G, int64_t W, const void* Craw, const void* Qraw, const float* mimg,
+                          const float* mcap, const int* cand, float lam, int gate, float* scores, void* workspace, hipStream_t st) {
+    FusedArgs a = xf_prep(Bi, Bj, G, W, Craw, Qraw, mimg, mcap, lam, gate, scores, workspace, st);
+    a.cand = cand; a.K = (int)K;
+    const FLds L = flds(a.Gr, a.Gk, a.Wp, a.Wk);
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xf_pairs_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xf_pairs_fwd_kernel, dim3((unsigned)K, (unsigned)Bi), dim3(512), (size_t)L.total, st, a);
     return 0;
 }

@@ -660,6 +660,20 @@ class XattnFn(torch.autograd.Function):
         return dC, dQ, None, None, None, None
 
 
+class XattnPairsFn(torch.autograd.Function):
+    """xattn_score_fast on an explicit list of (image, caption) pairs: [n_img, K] scores of (i, cand[i, k]).  Forward only (evaluation,
+    re-ranking); a backward through it raises."""
+
+    @staticmethod
+    def forward(ctx, im, s, im_m, s_m, cand, K, lam, gate):
+        return ops.xattn_pairs_fwd(im.contiguous(), s.contiguous(), im_m.contiguous().float(), s_m.contiguous().float(),
+                                   None if cand is None else cand.contiguous(), K, lam, gate)
+
+    @staticmethod
+    def backward(ctx, dscores):
+        raise ops._lib.DemoVLPHipError("the pair-list local similarity (dvlp_xattn_pairs_fwd) is forward only: it has no backward")
+
+
 class RWATailFn(torch.autograd.Function):
     """model/loss.py:105-116 on a given score matrix."""
 

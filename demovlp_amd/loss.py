@@ -72,6 +72,53 @@ class RWALoss(nn.Module):
                 sim[i0:i0 + rows] = out.cpu().numpy()
         return sim
 
+    def get_sim_pairs(self, im, s, im_m, s_l, s_m, cand=None, precision=None):
+        """[n_img, K] local similarity of image i and caption ``cand[i, k]`` only (not in the reference): the scores the multiple-choice
+        trainer reads off its K x K grid (trainer/trainer_dist.py:820-829), and the re-ranking of a global-similarity shortlist.
+
+        ``im`` [n_img, G, 256], ``s`` [n_cap, W, 256] with masks ``im_m`` [n_img, G], ``s_m`` [n_cap, W] (additive; None = no mask);
+        ``s_l`` is accepted and ignored, as in ``get_sim``.  ``cand``: integer [n_img, K] caption indices (host or device; repeats and any
+        order allowed); None means caption ``i * K + k`` with K = n_cap / n_img (the multiple-choice layout).  ``precision`` as in
+        ``get_sim_by_segment``.  bf16 within the fused kernel's range gives exactly the entries ``get_sim(...)[i, cand[i, k]]`` of the
+        fused full grid.  Forward only: with grad enabled on inputs that require grad this raises.  Returns fp32 on the device."""
+        if torch.is_grad_enabled() and (im.requires_grad or s.requires_grad):
+            raise DemoVLPHipError("get_sim_pairs is forward only (no backward): call it under torch.no_grad() or on detached inputs")
+        if im.dim() != 3 or s.dim() != 3:
+            raise ValueError(f"expected im [n_img, G, 256] and s [n_cap, W, 256], got {tuple(im.shape)} and {tuple(s.shape)}")
+        n_img, n_cap = im.shape[0], s.shape[0]
+        if cand is None:
+            if n_img == 0 or n_cap % n_img != 0:
+                raise ValueError(f"cand=None needs n_cap to be a multiple of n_img, got {n_cap} captions for {n_img} images")
+            K = n_cap // n_img
+        else:
+            if isinstance(cand, torch.Tensor):
+                if cand.dtype.is_floating_point or cand.dtype.is_complex or cand.dtype == torch.bool:
+                    raise ValueError(f"cand must hold integer caption indices, got {cand.dtype}")
+                c = cand.detach().cpu().numpy()
+            else:
+                c = np.asarray(cand)
+                if c.dtype.kind not in "iu":
+                    raise ValueError(f"cand must hold integer caption indices, got {c.dtype}")
+            if c.ndim != 2 or c.shape[0] != n_img or c.shape[1] < 1:
+                raise ValueError(f"cand must be [n_img={n_img}, K >= 1], got {tuple(c.shape)}")
+            if c.size and (c.min() < 0 or c.max() >= n_cap):
+                raise ValueError(f"cand indices must lie in [0, {n_cap}), got [{c.min()}, {c.max()}]")
+            K = c.shape[1]
+        if not im.is_cuda:                 # (the argument checks above are host logic and run first)
+            raise DemoVLPHipError("RWALoss runs on an MI355X device only (no CPU fallback)")
+        if cand is not None:
+            cand = torch.from_numpy(np.ascontiguousarray(c, dtype=np.int32)).to(im.device)
+        if precision is None:
+            precision = "bfloat16" if im.dtype == torch.bfloat16 and s.dtype == torch.bfloat16 else "float32"
+        if precision not in ("float32", "bfloat16"):
+            raise ValueError(f"precision must be None, 'float32' or 'bfloat16', got {precision!r}")
+        cd = torch.bfloat16 if precision == "bfloat16" else torch.float32
+        if s_m is None:
+            s_m = torch.zeros(s.shape[:2], device=im.device)
+        with torch.no_grad():
+            return Fn.XattnPairsFn.apply(im.to(cd), s.to(im.device).to(cd), im_m.to(im.device).float(), s_m.to(im.device).float(), cand, K,
+                                         float(self.lambda_softmax), self.focal_type == "equal")
+
     def forward(self, im, s, im_m, s_l, s_m):
         scores = self.get_sim(im, s, im_m, s_l, s_m)
         return Fn.RWATailFn.apply(scores, float(self.lambda_softmax))

@@ -62,3 +62,13 @@ def v2t_metrics(sims, query_masks=None):
             best = min(best, less + (eq - 1) / 2.0)
         ranks[ii] = best
     return cols2metrics(ranks, nq)
+
+
+def evaluate_mc(pred_id2answer, gt_id2answer):
+    """model/metric.py:275-295: multiple-choice accuracy over the PREDICTED ids (``shared_ids = pred_ids``, as the reference scores
+    them), formatted as the reference does: ``{'mc_accuracy': '<percent, 2 decimals>'}``."""
+    shared_ids = list(pred_id2answer.keys())
+    gt_answers = np.array([gt_id2answer[k] for k in shared_ids])
+    pred_answers = np.array([pred_id2answer[k] for k in shared_ids])
+    acc = np.mean(gt_answers == pred_answers)
+    return dict(mc_accuracy=f"{100 * acc:.2f}")

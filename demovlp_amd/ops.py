@@ -648,6 +648,21 @@ def xattn_bwd(C, Q, m_img, m_cap, lam, gate, dscores, ws):
     return dC, dQ
 
 
+def xattn_pairs_fwd(C, Q, m_img, m_cap, cand, K, lam, gate):
+    """C [Bi,G,256], Q [Bj,W,256] (compute dtype), additive fp32 masks, cand int32 [Bi,K] on the device or None (caption i*K + k)
+    -> scores fp32 [Bi,K] of the pairs (i, cand[i,k]); forward only, so the workspace is released on return."""
+    Bi, G, d = C.shape
+    Bj, W, _ = Q.shape
+    nbytes = call("dvlp_xattn_pairs_workspace_bytes", dt(C), Bi, Bj, int(K), G, W)
+    if nbytes < 0:
+        raise _lib.DemoVLPHipError(f"dvlp_xattn_pairs_workspace_bytes failed: {_lib.ERRORS.get(int(nbytes), nbytes)}")
+    ws = torch.empty(int(nbytes), device=C.device, dtype=torch.uint8)
+    scores = torch.empty((Bi, int(K)), device=C.device, dtype=torch.float32)
+    call("dvlp_xattn_pairs_fwd", dt(C), Bi, Bj, int(K), G, W, d, p(C), p(Q), p(m_img), p(m_cap), p(cand), float(lam), _gate_bits(gate),
+         p(scores), p(ws), stream())
+    return scores
+
+
 def global_local_loss(gt, go, xs, temperature, lam, use_global, use_local, stages, sim=None, dsim=None):
     """Raw call of the fused loss-head kernel.  Returns dict with whichever of sim/dsim/dgt/dgo/dxs/losses were produced."""
     ref = gt if gt is not None else (xs if xs is not None else sim)

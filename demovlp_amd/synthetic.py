@@ -327,3 +327,64 @@ def retrieval_batch(sd, num_frames: int, object_num: int, first: int, batch: int
         if npad:
             mask[b, F_ - 1, R - npad:] = 0.0                                   # a few padded regions: the mask path stays exercised
     return obj, mask, ids, att
+
+
+# multiple choice (MSRVTT-MC / LSMDC-MC layout, configs/ft/msrvtt_mc-select.json): question q shows clip `first + q` of the retrieval set
+# above and offers its caption among K - 1 distractors -- MC_SAME of them from the clip's own group of RETR_GROUP captions (one body word
+# apart), the rest from other groups (answer slot = q mod K).  Only MC_VISIBLE of the clip's regions stay in view (the others are masked
+# and zeroed), so the one word that tells the answer from its group mates is often out of view: with every region in view the reference
+# answers every question.
+MC_SAME, MC_VISIBLE = 3, 80
+
+
+def mc_questions(sd, num_frames: int, object_num: int, first: int, n: int, K: int = 5):
+    """Deterministic multiple-choice set on the retrieval set (weights ``sd`` = retrieval_state_dict).  Returns a dict:
+    ``object`` [n,F,R,2054] f32 / ``object_mask`` [n,F,R] f32 of clips first .. first + n - 1 (MC_VISIBLE regions in view, the rest masked and zeroed); ``input_ids`` / ``attention_mask``
+    [n*K, 100] int64, question-major (option k of question q is row q*K + k); ``options`` [n,K] int64 caption indices of the retrieval set;
+    ``answers`` [n] int64 (the slot holding caption first + q); ``mc_ids`` [n] int64 (= first + q)."""
+    if K < 1 or K > RETR_GROUP:
+        raise ValueError(f"K must lie in [1, {RETR_GROUP}], got {K}")
+    obj, mask, _, _ = retrieval_batch(sd, num_frames, object_num, first, n)
+    options = np.zeros((n, K), np.int64)
+    answers = np.zeros(n, np.int64)
+    n_same = min(MC_SAME, K - 1)
+    for q in range(n):
+        v = first + q
+        rng = np.random.default_rng(515151 + v)
+        grp = v // RETR_GROUP
+        mates = np.array([c for c in range(grp * RETR_GROUP, (grp + 1) * RETR_GROUP) if c != v])
+        same = rng.choice(mates, n_same, replace=False)
+        others = []
+        while len(others) < K - 1 - n_same:
+            c = int(rng.integers(0, 4096))
+            if c // RETR_GROUP != grp and c not in others:
+                others.append(c)
+        distract = np.concatenate([same, np.array(others, np.int64)]).astype(np.int64)
+        distract = distract[rng.permutation(K - 1)]
+        keep = rng.choice(np.flatnonzero(mask[q].reshape(-1) > 0), MC_VISIBLE, replace=False)
+        vis = np.zeros(mask[q].size, np.float32)
+        vis[keep] = 1.0
+        mask[q] = vis.reshape(mask[q].shape)
+        obj[q][mask[q] == 0] = 0.0                   # out of view: no feature either (the local term averages over every region, masked or not)
+        a = q % K
+        options[q] = np.concatenate([distract[:a], [v], distract[a:]])
+        answers[q] = a
+    ids = np.zeros((n * K, TEXT_LEN), np.int64)
+    att = np.zeros((n * K, TEXT_LEN), np.int64)
+    for r, c in enumerate(options.reshape(-1)):
+        ids[r:r + 1], att[r:r + 1] = retrieval_captions(int(c), 1)
+    return dict(object=obj, object_mask=mask, input_ids=ids, attention_mask=att, options=options, answers=answers,
+                mc_ids=np.arange(first, first + n, dtype=np.int64))
+
+
+def mc_batches(mc, Q: int, device=None):
+    """Batches of Q questions of an ``mc_questions`` set in the layout ``trainer.evaluate_mc`` reads: ``{'text': {input_ids,
+    attention_mask} [Q*K, 100], 'object' [Q,F,R,2054], 'object_mask' [Q,F,R], 'mc_id': list of Q}`` (torch tensors on ``device``)."""
+    import torch
+    n, K = mc["options"].shape
+    for q0 in range(0, n, Q):
+        q1 = min(n, q0 + Q)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device) if device is not None else torch.from_numpy(np.ascontiguousarray(a))
+        yield {"text": {"input_ids": t(mc["input_ids"][q0 * K:q1 * K]), "attention_mask": t(mc["attention_mask"][q0 * K:q1 * K])},
+               "object": t(mc["object"][q0:q1]), "object_mask": t(mc["object_mask"][q0:q1]),
+               "mc_id": [int(x) for x in mc["mc_ids"][q0:q1]]}

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import warnings
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -1129,3 +1130,78 @@ def evaluate(model, loss_fn, batches, metrics=None, use_local=True, mscoco=False
     for fn in metrics:
         nested[fn.__name__] = fn(o2t_sims, fold=5) if mscoco else fn(o2t_sims)
     return dict(val_loss=total / max(nb, 1), o2t_sims=o2t_sims, global_sims=global_sims, local_sims=local_sims, nested_val_metrics=nested)
+
+
+def gather_mc_results(mc_ids, preds, scores, group=None):
+    """The (mc_id, prediction, score row) triples of every rank, merged in rank order and returned on EVERY rank -- the collective that
+    replaces the reference's per-rank JSON files, barrier and rank-0 merge (trainer/trainer_dist.py:831-847).  Without a process group
+    (or with one rank) the input is returned as it is.  -> (pred_id2answer dict, scores numpy [N, K])."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    parts = [(list(mc_ids), [int(p) for p in preds], np.asarray(scores))]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (list(mc_ids), [int(p) for p in preds], np.asarray(scores)), group=group)
+    pred_id2answer = {}
+    for ids, pr, _ in parts:
+        pred_id2answer.update(zip(ids, pr))
+    rows = [s for _, _, s in parts if len(s)]
+    K = next((s.shape[1] for s in rows), 0)
+    return pred_id2answer, (np.concatenate(rows) if rows else np.zeros((0, K), np.float32))
+
+
+def evaluate_mc(model, loss_fn, batches, gt_id2answer, metrics=None, precision=None, global_term="reference"):
+    """Multiple-choice evaluation of one validation loader, mirroring ``Multi_ObjectMCTrainer_dist._valid_epoch`` (trainer/trainer_dist.py:
+    771-893) on already-tokenised batches ``{'text': {input_ids, attention_mask} [Q*K, L] (question-major), 'object' [Q,F,R,2054],
+    'object_mask' [Q,F,R], 'mc_id': list of Q}``; Q = 1 is the reference's own layout (batch_size 1).
+
+    The reference ``expand``s each clip to its K options and runs the object tower on the K identical copies; here the object tower runs
+    once per clip and the text tower on the Q*K options.  ``text_length`` / ``text_mask`` are built as at :808-811.  The local term is
+    ``RWALoss.get_sim_pairs`` (clip q against its own K options only -- the reference computes the K x K grid and reads row 0), with the
+    loss' ``lambda_softmax`` / ``focal_type``; ``precision`` is handed to it (None follows the embeddings).  The prediction is the first
+    maximal option, on the host (``sims_batch[0].max(0)[1]``).
+
+    ``global_term``:
+      ``'reference'`` (default) reproduces the reference: its global addend is ``sim_matrix(text, object)[0]`` -- option 0 against the K
+                      identical copies of the clip -- so every option gets the same ``cos(t_{q,0}, v_q)`` and only the local term decides.
+      ``'per_option'`` adds ``cos(t_{q,k}, v_q)`` to option k instead.  This DEPARTS from the reference (its accuracies are not comparable
+                      with the reference's numbers); opt in explicitly.
+
+    With a process group of more than one rank, each rank evaluates its own batches and the (mc_id, prediction) pairs are gathered with
+    ``torch.distributed`` collectives (``gather_mc_results``); every rank returns the merged result.  The model's train / eval mode is
+    restored on exit.  Returns ``{'pred_id2answer', 'scores' (numpy [N, K], fp32 global + local), 'nested_val_metrics': {name: result}}``."""
+    from . import metric as M
+    if global_term not in ("reference", "per_option"):
+        raise ValueError(f"global_term must be 'reference' or 'per_option', got {global_term!r}")
+    metrics = metrics if metrics is not None else (M.evaluate_mc,)
+    local_loss = getattr(loss_fn, "local_loss", loss_fn)
+    ids, preds, rows = [], [], []
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for data in batches:
+                att = data["text"]["attention_mask"]
+                Q = data["object"].shape[0]
+                if Q == 0 or att.shape[0] % Q != 0 or len(data["mc_id"]) != Q:
+                    raise ValueError(f"expected Q*K option rows and Q mc_ids for Q = {Q} clips, got {att.shape[0]} rows, {len(data['mc_id'])} ids")
+                K = att.shape[0] // Q
+                text_length = torch.sum(att, dim=1)
+                text_mask = (att[:, 1:] - 1.0) * 100.0
+                out = model(data, return_embeds=True)
+                g = sim_matrix(out["global_text_embeddings"], out["global_object_embeddings"]).view(Q, K, Q)
+                q = torch.arange(Q, device=g.device)
+                g = g[q, :, q]                                                # [Q, K]: cos(t_{q,k}, v_q)
+                if global_term == "reference":
+                    g = g[:, :1].expand(Q, K)
+                loc = local_loss.get_sim_pairs(out["local_object_embeddings"], out["local_text_embeddings"], out["object_mask"], text_length,
+                                               text_mask, cand=None, precision=precision)
+                s = (g.float() + loc).cpu().numpy()
+                rows.append(s)
+                preds.extend(int(p) for p in np.argmax(s, axis=1))           # first maximal index
+                ids.extend(data["mc_id"])
+    finally:
+        model.train(was_training)
+    scores = np.concatenate(rows) if rows else np.zeros((0, 0), np.float32)
+    pred_id2answer, scores = gather_mc_results(ids, preds, scores)
+    nested = {fn.__name__: fn(pred_id2answer, gt_id2answer) for fn in metrics}
+    return dict(pred_id2answer=pred_id2answer, scores=scores, nested_val_metrics=nested)

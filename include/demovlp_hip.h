@@ -206,6 +206,16 @@ int dvlp_xattn_fwd(int dtype, int64_t Bi, int64_t Bj, int64_t G, int64_t W, int6
 int dvlp_xattn_bwd(int dtype, int64_t Bi, int64_t Bj, int64_t G, int64_t W, int64_t d, const void* Craw, const void* Qraw,
                    const float* mimg, const float* mcap, float lam, int gate, const float* dscores, void* workspace, void* dC,
                    void* dQ, void* stream);
+/* Pair list (forward only): scores[i][k] = the local similarity above of video i (Craw [Bi][G][d], mimg [Bi][G]) and caption cand[i K + k] of
+   the pool Qraw [Bj][W][d] / mcap [Bj][W]; cand is an int32 [Bi][K] device array, NULL meaning caption i K + k (the multiple-choice layout,
+   trainer/trainer_dist.py:820-829, without its K x K grid).  A cand entry outside [0, Bj) reads nothing and scores NaN.  bf16 within the
+   fused kernel's range (G <= 288, W <= 112): one prep of the Bi videos and Bj captions, then one workgroup per pair -- the per-pair code of
+   the full-grid fused kernel, so scores[i][k] equals its entry [i][cand[i K + k]] bit for bit.  Otherwise the multi-kernel path scores each
+   video against its K gathered captions.  Workspace sizes return a negative DVLP_ERR_* for a bad dtype / shape. */
+int64_t dvlp_xattn_pairs_workspace_bytes(int dtype, int64_t Bi, int64_t Bj, int64_t K, int64_t G, int64_t W);
+int dvlp_xattn_pairs_fwd(int dtype, int64_t Bi, int64_t Bj, int64_t K, int64_t G, int64_t W, int64_t d, const void* Craw, const void* Qraw,
+                         const float* mimg, const float* mcap, const int* cand, float lam, int gate, float* scores, void* workspace,
+                         void* stream);
 
 /* ---- loss heads: sim_matrix (model/model.py:582-590) + NormSoftmaxLoss (model/loss.py:126-138) + RWALoss tail
  *      (model/loss.py:105-116) + GlobalLocalLoss sum (:29-45); forward and analytic gradients in one launch        ---- */
