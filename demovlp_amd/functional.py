@@ -687,3 +687,132 @@ class RWATailFn(torch.autograd.Function):
     def backward(ctx, g):
         (dxs,) = ctx.saved_tensors
         return dxs * g, None
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# video-QA answer head (model/video_qa_mdoel.py:56-97, model/model.py:281-289, model/loss.py:180-187; csrc/qahead.hip)
+# ----------------------------------------------------------------------------------------------------------------
+class WeightNormFoldFn(torch.autograd.Function):
+    """``apply(bf16_of, v_0, g_0, v_1, g_1, ...) -> (W_0, ..., W_{n-1}, bf16 copy of W_i for i in bf16_of ...)``: W = g V / |V|_F
+    (weight_norm, dim=None) of all tensors in one launch; the backward turns every dW into dV and dg in one launch."""
+
+    @staticmethod
+    def forward(ctx, bf16_of, *vg):
+        vs, gs = list(vg[0::2]), list(vg[1::2])
+        W, Wb, norms = ops.wn_fold_fwd(vs, gs, want_bf16=bf16_of)
+        ctx.save_for_backward(norms, *vg)
+        ctx.n = len(vs)
+        extra = [Wb[i] for i in bf16_of]
+        ctx.mark_non_differentiable(*extra)
+        return (*W, *extra)
+
+    @staticmethod
+    def backward(ctx, *d):
+        norms, *vg = ctx.saved_tensors
+        vs, gs = vg[0::2], vg[1::2]
+        dWs = [d[i] if d[i] is not None else torch.zeros_like(vs[i]) for i in range(ctx.n)]
+        dV, dg = ops.wn_fold_bwd(vs, gs, dWs, norms)
+        out = [None]
+        for a, b in zip(dV, dg):
+            out += [a, b]
+        return tuple(out)
+
+
+class TokenMaxFn(torch.autograd.Function):
+    """``torch.max(x, dim=1)[0]`` for x [B, T, d] in either compute dtype -> fp32 [B, d]; ties go to the first token."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ops.require_gpu(x)
+        x = x.contiguous()
+        out, idx = ops.token_max_fwd(x)
+        ctx.save_for_backward(idx)
+        ctx.meta = (x.shape[1], x.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (idx,) = ctx.saved_tensors
+        T, dtype = ctx.meta
+        return ops.token_max_bwd(dout.float().contiguous(), idx, T, dtype)
+
+
+class QAAttendFn(torch.autograd.Function):
+    """Attention.forward + the weighted region sum of BUTDQAHead: ``apply(v, mask, q, Wq, bq, Wv, Wv_bf16, bv, wl, bl, drop) -> (pooled, att)``
+    with the FOLDED weights.  v [B, G, 256] is read through its strides (``object_embeddings[:, 1:]`` is not copied).  bf16 with G <= 288 runs
+    the fused MFMA kernel; otherwise H = v Wv^T + bv is one dvlp_gemm launch and the rest its epilogue kernel.  ``drop``: None or
+    (p, Philox state, site).  The two large gradient products (dv += dH Wv, dWv = dH^T v) are dvlp_gemm launches."""
+
+    @staticmethod
+    def forward(ctx, v, mask, q, Wq, bq, Wv, Wv_b, bv, wl, bl, drop):
+        ops.require_gpu(v, mask, q)
+        B, G, d = v.shape
+        if d != 256 or q.shape != (B, 256) or mask.shape != (B, G):
+            raise ops._lib.DemoVLPHipError(f"QAAttendFn: expected v [B, G, 256], mask [B, G], q [B, 256], got {tuple(v.shape)}, "
+                                           f"{tuple(mask.shape)}, {tuple(q.shape)}")
+        v, P = ops.qa_row_layout(v.detach())
+        mask, q = mask.float().contiguous(), q.float().contiguous()
+        rows = (B - 1) * P + G
+        fused = Wv_b is not None and ops.qa_attend_fused(v.dtype, G)
+        H = None
+        if not fused:
+            Wc = Wv if v.dtype == torch.float32 else (Wv_b if Wv_b is not None else Wv.to(v.dtype))
+            H = ops.gemm(v, Wc, rows, d, d, bias=bv)
+        qp, att, pooled, snap = ops.qa_attend_fwd(v, P, mask, q, Wq, bq, Wv_b if fused else None, bv, wl, bl, H, drop)
+        ctx.save_for_backward(v, mask, q, Wq, Wv, Wv_b, bv, wl, H, qp, att, snap)
+        ctx.meta = (P, fused, drop[0] if drop is not None else 0.0, drop[2] if drop is not None else 0)
+        ctx.mark_non_differentiable(att)
+        return pooled, att
+
+    @staticmethod
+    def backward(ctx, dpooled, _datt):
+        v, mask, q, Wq, Wv, Wv_b, bv, wl, H, qp, att, snap = ctx.saved_tensors
+        P, fused, prob, site = ctx.meta
+        B, G, d = v.shape
+        rows = (B - 1) * P + G
+        dv, dH, dq, dWq, dbq, dbv, dwl, dbl = ops.qa_attend_bwd(v, P, mask, q, Wq, Wv_b if fused else None, bv, wl, H, prob, snap, site, qp, att,
+                                                                dpooled.float().contiguous())
+        Wc = Wv if v.dtype == torch.float32 else (Wv_b if Wv_b is not None else Wv.to(v.dtype))
+        ops.linear_bwd_input(dH, Wc, out=dv, accumulate=True)
+        dWv = ops.linear_bwd_weight(dH, v.as_strided((rows, d), (d, 1)))
+        return dv.as_strided((B, G, d), (P * d, d, 1)), None, dq, dWq, dbq, dWv, None, dbv, dwl.view(1, d), dbl, None
+
+
+class PlainLinearFn(torch.autograd.Function):
+    """y = x W^T + b for a weight that is not a Parameter (a folded weight-norm weight): the launches of LinearFn, gradients returned to
+    autograd."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        y = ops.linear_fwd(x2, w.detach(), b.detach())
+        ctx.save_for_backward(x2, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w = ctx.saved_tensors
+        dy2 = dy.contiguous()
+        return ops.linear_bwd_input(dy2, w.detach()), ops.linear_bwd_weight(dy2, x2), ops.colsum(dy2)
+
+
+class SoftmaxXentFn(torch.autograd.Function):
+    """nn.CrossEntropyLoss (mean) on fp32 logits [B, C] with int64 labels: ``apply(logits, labels) -> (loss scalar, pred int32 [B])``; the
+    gradient and the arg-max come out of the same pass."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        ops.require_gpu(logits, labels)
+        if logits.dim() != 2 or labels.dtype != torch.int64 or labels.shape != logits.shape[:1]:
+            raise ops._lib.DemoVLPHipError(f"SoftmaxXentFn: expected logits [B, C] and int64 labels [B], got {tuple(logits.shape)} and "
+                                           f"{labels.dtype} {tuple(labels.shape)}")
+        loss, dlog, pred = ops.softmax_xent(logits.detach().float().contiguous(), labels.contiguous(), want_grad=True)
+        ctx.save_for_backward(dlog)
+        ctx.in_dtype = logits.dtype
+        ctx.mark_non_differentiable(pred)
+        return loss.reshape(()), pred
+
+    @staticmethod
+    def backward(ctx, dloss, _dpred):
+        (dlog,) = ctx.saved_tensors
+        return (dlog * dloss).to(ctx.in_dtype), None

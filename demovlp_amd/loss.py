@@ -125,13 +125,22 @@ class RWALoss(nn.Module):
 
 
 class CrossEntropy(nn.Module):
-    """model/loss.py:180-187: the QA fine-tuning loss (configs/ft/*_qa-select.json), on the [B, num_label] logits of ObjectQARelation."""
+    """model/loss.py:180-187: the QA fine-tuning loss (configs/ft/*_qa-select.json), on the [B, num_label] logits of ObjectQARelation.
+    ``impl="hip"`` (not in the reference's signature) computes the mean loss, its gradient and the arg-max predictions in one pass
+    (``dvlp_softmax_xent``); the predictions of the last call are ``last_pred`` (int32 [B]).  The default is nn.CrossEntropyLoss."""
 
-    def __init__(self):
+    def __init__(self, impl="stock"):
         super().__init__()
+        if impl not in ("stock", "hip"):
+            raise ValueError(f"impl must be 'stock' or 'hip', got {impl!r}")
+        self.impl = impl
+        self.last_pred = None
         self.loss = nn.CrossEntropyLoss()
 
     def forward(self, output, target):
+        if self.impl == "hip":
+            loss, self.last_pred = Fn.SoftmaxXentFn.apply(output, target)
+            return loss
         return self.loss(output, target)
 
 

@@ -72,3 +72,27 @@ def evaluate_mc(pred_id2answer, gt_id2answer):
     pred_answers = np.array([pred_id2answer[k] for k in shared_ids])
     acc = np.mean(gt_answers == pred_answers)
     return dict(mc_accuracy=f"{100 * acc:.2f}")
+
+
+QA_ANSWER_TYPES = ("what", "who", "how", "where", "when", "object", "number", "color", "location")
+
+
+def evaluate_qa(results, label2ans, qid2data):
+    """model/metric.py:217-272 (MSRVTT-QA score): ``results`` is a list of ``{'question_id', 'answer': class index}``; a repeated question
+    id keeps its LAST entry, as the reference's dict does.  Returns ``overall_acc``, one ``<type>_acc`` per answer type (0 for a type without
+    questions) and ``ratios`` = ``{'<type>_ratio': [share of the questions, count]}``.  The reference also prints the per-type counts."""
+    last = {}
+    for r in results:
+        last[r["question_id"]] = r["answer"]
+    preds = np.array([label2ans[a] for a in last.values()])
+    gts = np.array([qid2data[q]["answer"] for q in last])
+    types = np.array([QA_ANSWER_TYPES.index(qid2data[q]["answer_type"]) for q in last], dtype=np.int64)
+    hit = preds == gts
+    out = {"overall_acc": float(np.mean(hit))}
+    ratios = {}
+    for i, name in enumerate(QA_ANSWER_TYPES):
+        sel = hit[types == i]
+        out[f"{name}_acc"] = float(np.mean(sel)) if len(sel) != 0 else 0
+        ratios[f"{name}_ratio"] = [1.0 * len(sel) / len(types), len(sel)]
+    out["ratios"] = ratios
+    return out

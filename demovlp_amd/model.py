@@ -180,10 +180,10 @@ class ObjectQARelation(ObjectRelation):
     embeddings with the loader's 0/1 region mask."""
 
     def __init__(self, object_params, text_params, projection_dim=256, load_checkpoint=None, projection="minimal",
-                 load_temporal_fix="bilinear", compute_dtype="float32", pretrained_init=True):
+                 load_temporal_fix="bilinear", compute_dtype="float32", pretrained_init=True, head_impl="stock"):
         super().__init__(object_params, text_params, projection_dim, None, projection, load_temporal_fix, compute_dtype, pretrained_init)
         from .video_qa_model import BUTDQAHead
-        self.head = BUTDQAHead(v_dim=256, q_dim=256, hid_dim=256, out_dim=object_params["num_label"])
+        self.head = BUTDQAHead(v_dim=256, q_dim=256, hid_dim=256, out_dim=object_params["num_label"], impl=head_impl)
         if load_checkpoint not in ["", None]:
             checkpoint = torch.load(load_checkpoint, map_location="cpu")
             new_state_dict = self._inflate_positional_embeds(state_dict_data_parallel_fix(checkpoint["state_dict"], self.state_dict()))
@@ -208,6 +208,8 @@ class ObjectQARelation(ObjectRelation):
         if object_mask.dim() == 3:
             object_mask = object_mask.reshape(object_mask.shape[0], -1)
         object_mask = object_mask.to(torch.float32)
+        if self.head.impl == "hip":          # the embeddings go over as they are: no .float() copies, object_embeddings[:, 1:] is read in place
+            return self.head(Fn.TokenMaxFn.apply(text_embeddings), object_embeddings[:, 1:], object_mask)
         text_embeddings, _ = torch.max(text_embeddings.float(), dim=1)
         return self.head(text_embeddings, object_embeddings[:, 1:].float(), object_mask)
 

@@ -501,6 +501,116 @@ def attn_keep_masks(B, L, prob, state, site, device):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# video-QA answer head (csrc/qahead.hip)
+# ----------------------------------------------------------------------------------------------------------------
+QA_HEAD_DROPOUT_SITE = 32        # Philox site of the head's Attention dropout (the text tower uses 0 .. 12: text_model.py, functional.py)
+
+
+def _ptr_table(ts):
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def wn_fold_fwd(vs, gs, want_bf16=()):
+    """weight_norm(dim=None) of several tensors in one launch: -> (list of folded fp32 W, list of bf16 copies or None, norms [n] fp32).
+    ``want_bf16``: indices that also get a bf16 copy."""
+    require_gpu(*vs, *gs)
+    n = len(vs)
+    vs = [v.detach().contiguous() for v in vs]
+    gs = [g.detach().contiguous() for g in gs]
+    W = [torch.empty_like(v) for v in vs]
+    Wb = [torch.empty_like(v, dtype=torch.bfloat16) if i in want_bf16 else None for i, v in enumerate(vs)]
+    norms = torch.empty(n, device=vs[0].device, dtype=torch.float32)
+    call("dvlp_wn_fold_fwd", n, _ptr_table(vs), _ptr_table(gs), (ctypes.c_int64 * n)(*[v.numel() for v in vs]), _ptr_table(W), _ptr_table(Wb),
+         p(norms), stream())
+    return W, Wb, norms
+
+
+def wn_fold_bwd(vs, gs, dWs, norms):
+    """-> (list of dV, list of dg) from the gradients of the folded weights (one launch)."""
+    n = len(vs)
+    vs = [v.detach().contiguous() for v in vs]
+    gs = [g.detach().contiguous() for g in gs]
+    dWs = [d.contiguous() for d in dWs]
+    dV = [torch.empty_like(v) for v in vs]
+    dg = [torch.empty_like(g) for g in gs]
+    call("dvlp_wn_fold_bwd", n, _ptr_table(vs), _ptr_table(gs), (ctypes.c_int64 * n)(*[v.numel() for v in vs]), _ptr_table(dWs), p(norms),
+         _ptr_table(dV), _ptr_table(dg), stream())
+    return dV, dg
+
+
+def token_max_fwd(x):
+    """x [B, T, d] -> (max over T as fp32 [B, d], int32 index of the first maximal token)."""
+    B, T, d = x.shape
+    out = torch.empty((B, d), device=x.device, dtype=torch.float32)
+    idx = torch.empty((B, d), device=x.device, dtype=torch.int32)
+    call("dvlp_token_max_fwd", dt(x), B, T, d, p(x), p(out), p(idx), stream())
+    return out, idx
+
+
+def token_max_bwd(dout, idx, T, dtype):
+    B, d = dout.shape
+    dx = torch.empty((B, T, d), device=dout.device, dtype=dtype)
+    call("dvlp_token_max_bwd", dt(dtype), B, T, d, p(dout), p(idx), p(dx), stream())
+    return dx
+
+
+def qa_attend_fused(dtype, G) -> bool:
+    return bool(call("dvlp_qa_attend_fused", dt(dtype), G))
+
+
+def qa_row_layout(v):
+    """(v to read, rows per sample P) for a [B, G, 256] view: when the samples lie a whole number of rows apart (a contiguous tensor, or
+    ``x[:, 1:]`` of one), v is read in place and row b P + g of its storage, counted from v's first element, is region g of sample b;
+    anything else is copied once."""
+    B, G, d = v.shape
+    if not (v.stride(2) == 1 and v.stride(1) == d and v.stride(0) % d == 0 and v.stride(0) >= G * d and v.data_ptr() % 16 == 0):
+        v = v.contiguous()
+    return v, (v.stride(0) // d if B > 1 else G)
+
+
+def qa_attend_fwd(v, P, mask, q, Wq, bq, Wv_b, bv, wl, bl, H, drop):
+    """-> (qp, att, pooled, state snapshot | None).  ``drop``: None or (p, state, site).  ``H``: None = the fused route."""
+    B, G, d = v.shape
+    dev = v.device
+    qp = torch.empty((B, d), device=dev, dtype=torch.float32)
+    att = torch.empty((B, G), device=dev, dtype=torch.float32)
+    pooled = torch.empty((B, d), device=dev, dtype=torch.float32)
+    prob, state, site = drop if drop is not None else (0.0, None, 0)
+    snap = torch.empty(4, device=dev, dtype=torch.int32) if drop is not None else None
+    call("dvlp_qa_attend_fwd", dt(v), B, G, p(v), P * d, d, p(mask), p(q), p(Wq), p(bq), p(Wv_b), p(bv), p(wl), p(bl), p(H), P, float(prob),
+         p(state), int(site), p(snap), p(qp), p(att), p(pooled), stream())
+    return qp, att, pooled, snap
+
+
+def qa_attend_bwd(v, P, mask, q, Wq, Wv_b, bv, wl, H, drop_p, snap, site, qp, att, d_pooled):
+    """-> (dv rows, dH rows, dq, dWq, dbq, dbv, dwl, dbl); dv / dH are [(B - 1) P + G, 256] in v's dtype (row b P + g); the rows of dH
+    between two samples' regions are zero."""
+    B, G, d = v.shape
+    dev = v.device
+    rows = (B - 1) * P + G
+    dv = (torch.empty if P == G else torch.zeros)((rows, d), device=dev, dtype=v.dtype)
+    dH = (torch.empty if P == G else torch.zeros)((rows, d), device=dev, dtype=v.dtype)
+    f = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
+    dq, dWq, dbq, dbv, dwl, dbl = f(B, d), f(d, d), f(d), f(d), f(d), f(1)
+    ws = f(int(call("dvlp_qa_attend_workspace_floats", B, G)))
+    call("dvlp_qa_attend_bwd", dt(v), B, G, p(v), P * d, d, p(mask), p(q), p(Wq), p(Wv_b), p(bv), p(wl), p(H), P, float(drop_p), p(snap), int(site),
+         p(qp), p(att), p(d_pooled), p(dv), p(dH), p(dq), p(dWq), p(dbq), p(dbv), p(dwl), p(dbl), p(ws), stream())
+    return dv, dH, dq, dWq, dbq, dbv, dwl, dbl
+
+
+def softmax_xent(logits, labels, want_grad=True):
+    """-> (mean loss [1], dlogits | None, pred int32 [B])."""
+    B, C = logits.shape
+    dev = logits.device
+    rows = torch.empty(B, device=dev, dtype=torch.float32)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    pred = torch.empty(B, device=dev, dtype=torch.int32)
+    dlog = torch.empty_like(logits) if want_grad else None
+    call("dvlp_softmax_xent", B, C, p(logits), p(labels), p(rows), p(dlog), p(pred), p(loss), stream())
+    return loss, dlog, pred
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # prologues
 # ----------------------------------------------------------------------------------------------------------------
 def obj_split(obj, dtype):

@@ -388,3 +388,55 @@ def mc_batches(mc, Q: int, device=None):
         yield {"text": {"input_ids": t(mc["input_ids"][q0 * K:q1 * K]), "attention_mask": t(mc["attention_mask"][q0 * K:q1 * K])},
                "object": t(mc["object"][q0:q1]), "object_mask": t(mc["object_mask"][q0:q1]),
                "mc_id": [int(x) for x in mc["mc_ids"][q0:q1]]}
+
+
+# video question answering (MSRVTT-QA layout, configs/ft/msrvtt_qa-select.json): question i shows clip `first + i` of the retrieval set.  Its
+# text is QA_WORDS body words of the clip's own caption in caption order (so the text tower sees words the clip's regions were aimed at) with
+# one of them, at a position the question's own generator picks, replaced by a "query" word from a pool of QA_QUERY_POOL ids; the answer is
+# (query word index + group of the clip) mod num_label: it depends on the clip AND on the question, and neither alone determines it.
+QA_WORDS, QA_QUERY_POOL = 8, 16
+
+
+def qa_questions(sd, num_frames: int, object_num: int, first: int, n: int, num_label: int):
+    """Deterministic QA set on the retrieval set (weights ``sd`` = retrieval_state_dict).  Returns a dict: ``object`` [n,F,R,2054] f32,
+    ``object_mask`` [n,F,R] f32, ``input_ids`` / ``attention_mask`` [n,100] int64, ``label`` [n] int64 in [0, num_label), ``question_id`` [n]
+    int64 (= first + i), ``answer_type`` (list of n names cycling through metric.QA_ANSWER_TYPES), ``label2ans`` (list of num_label answer
+    strings) and ``qid2data`` ({question_id: {'answer', 'answer_type'}}, what metric.evaluate_qa reads)."""
+    from .metric import QA_ANSWER_TYPES
+    if num_label < 2:
+        raise ValueError(f"num_label must be at least 2, got {num_label}")
+    obj, mask, cap_ids, _ = retrieval_batch(sd, num_frames, object_num, first, n)
+    ids = np.zeros((n, TEXT_LEN), np.int64)
+    att = np.zeros((n, TEXT_LEN), np.int64)
+    label = np.zeros(n, np.int64)
+    pool = np.random.default_rng(606060).choice(np.arange(1000, VOCAB), QA_QUERY_POOL, replace=False)
+    for i in range(n):
+        v = first + i
+        rng = np.random.default_rng(717171 + v)
+        keep = np.sort(rng.choice(RETR_WORDS, QA_WORDS, replace=False))
+        body = cap_ids[i, 1 + keep].copy()
+        k = int(rng.integers(0, QA_QUERY_POOL))
+        body[int(rng.integers(0, QA_WORDS))] = pool[k]
+        m = QA_WORDS + 2
+        ids[i, 0], ids[i, 1:m - 1], ids[i, m - 1] = 101, body, 102
+        att[i, :m] = 1
+        label[i] = (k + v // RETR_GROUP) % num_label
+    label2ans = [f"answer{j}" for j in range(num_label)]
+    types = [QA_ANSWER_TYPES[(first + i) % len(QA_ANSWER_TYPES)] for i in range(n)]
+    qids = np.arange(first, first + n, dtype=np.int64)
+    qid2data = {int(q): {"answer": label2ans[int(l)], "answer_type": t} for q, l, t in zip(qids, label, types)}
+    return dict(object=obj, object_mask=mask, input_ids=ids, attention_mask=att, label=label, question_id=qids, answer_type=types,
+                label2ans=label2ans, qid2data=qid2data)
+
+
+def qa_batches(qa, Q: int, device=None):
+    """Batches of Q questions of a ``qa_questions`` set in the layout ``trainer.train_step_qa`` / ``trainer.evaluate_qa`` read: ``{'text':
+    {input_ids, attention_mask}, 'object', 'object_mask', 'label', 'question_id'}`` (torch tensors on ``device``)."""
+    import torch
+    n = len(qa["label"])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device) if device is not None else torch.from_numpy(np.ascontiguousarray(a))
+    for q0 in range(0, n, Q):
+        q1 = min(n, q0 + Q)
+        yield {"text": {"input_ids": t(qa["input_ids"][q0:q1]), "attention_mask": t(qa["attention_mask"][q0:q1])},
+               "object": t(qa["object"][q0:q1]), "object_mask": t(qa["object_mask"][q0:q1]), "label": t(qa["label"][q0:q1]),
+               "question_id": t(qa["question_id"][q0:q1])}

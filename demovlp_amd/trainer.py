@@ -1205,3 +1205,100 @@ def evaluate_mc(model, loss_fn, batches, gt_id2answer, metrics=None, precision=N
     pred_id2answer, scores = gather_mc_results(ids, preds, scores)
     nested = {fn.__name__: fn(pred_id2answer, gt_id2answer) for fn in metrics}
     return dict(pred_id2answer=pred_id2answer, scores=scores, nested_val_metrics=nested)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# video question answering (train_dist_multi_qa.py, Multi_ObjectQATrainer_dist: trainer/trainer_dist.py:421-701)
+# ----------------------------------------------------------------------------------------------------------------
+def train_step_qa(model, loss_fn, optimizer, data, reducer: GradReducer | None = None):
+    """One QA optimisation step on an already-tokenised, already-on-device batch ``{'text': {input_ids, attention_mask}, 'object',
+    'object_mask', 'label' int64 [B]}`` (trainer/trainer_dist.py:521-560): zero_grad, forward, ``loss_fn(logits, label)``, the accuracy count
+    of :545-546, backward, step.  Built like ``train_step``: a ``FusedAdamW`` spreads its update over the backward when there is no gradient
+    exchange, a ``GradReducer`` exchanges the buckets, an exception leaves the optimizer usable.  -> (detached loss, number of correct
+    predictions as a 0-d int64 tensor on the device; no host synchronisation here)."""
+    optimizer.zero_grad()
+    if reducer is not None:
+        reducer.begin()
+    elif isinstance(optimizer, FusedAdamW) and not (dist.is_initialized() and dist.get_world_size() > 1):
+        optimizer.begin_overlapped()
+    try:
+        label = data["label"]
+        logits = model(data)["logits"]
+        loss = loss_fn(logits, label)
+        pred = getattr(loss_fn, "last_pred", None) if getattr(loss_fn, "impl", "stock") == "hip" else None
+        if pred is None:
+            pred = logits.detach().max(dim=-1)[1]
+        n_correct = (pred.to(label.dtype) == label).long().sum()
+        loss.backward()
+        if loss.is_cuda:
+            Fn.join_side_stream()
+        backward_second(model)
+        scale = reducer.finish() if reducer is not None else 1.0
+    except BaseException:
+        if isinstance(optimizer, FusedAdamW):
+            optimizer.abort_overlapped()
+        raise
+    if isinstance(optimizer, FusedAdamW):
+        optimizer.step(grad_scale=scale)
+    else:
+        if scale != 1.0:
+            for p in model.parameters():
+                if p.grad is not None:
+                    p.grad.mul_(scale)
+        optimizer.step()
+    return loss.detach(), n_correct
+
+
+def gather_qa_results(qids, logits, group=None):
+    """Question ids [n] and logits [n, C] of every rank, concatenated in rank order and returned on EVERY rank (the per-batch all_gather of
+    trainer/trainer_dist.py:620-641; ranks may hold different numbers of questions).  Without a process group, or with one rank, the inputs
+    come back as they are.  -> (int64 tensor [N], float tensor [N, C]), both on the host."""
+    qids = torch.as_tensor(qids).detach().to("cpu", torch.int64).reshape(-1)
+    logits = torch.as_tensor(logits).detach().to("cpu").float()
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    if world <= 1:
+        return qids, logits
+    parts = [None] * world
+    dist.all_gather_object(parts, (qids.numpy(), logits.numpy()), group=group)
+    parts = [(q, l) for q, l in parts if len(q)]
+    if not parts:
+        return qids, logits
+    return torch.from_numpy(np.concatenate([q for q, _ in parts])), torch.from_numpy(np.concatenate([l for _, l in parts]))
+
+
+def evaluate_qa(model, batches, label2ans, qid2data, metrics=None, precision=None):
+    """QA evaluation of one validation loader, mirroring ``Multi_ObjectQATrainer_dist._valid_epoch`` (trainer/trainer_dist.py:597-683) on
+    already-tokenised batches ``{'text', 'object', 'object_mask', 'question_id' int64 [B]}``: eval mode (the previous mode is restored on
+    exit), no gradients, per batch the question ids and logits of every rank are gathered (``gather_qa_results``), the prediction is the first
+    maximal class (``logits.max(dim=-1)[1]``), and the reference's ``results`` list -- ``{'question_id', 'answer', 'data'}`` per question, in
+    batch order -- goes to every metric (default ``metric.evaluate_qa``).  ``precision``: None, or 'float32' / 'bfloat16' to assert the dtype
+    the model computes in (a model's compute dtype is fixed when it is built).
+    -> ``{'results', 'question_ids' (numpy [N]), 'logits' (numpy [N, C] fp32), 'preds' (numpy [N]), 'nested_val_metrics': {name: dict}}``."""
+    from . import metric as M
+    if precision not in (None, "float32", "bfloat16"):
+        raise ValueError(f"precision must be None, 'float32' or 'bfloat16', got {precision!r}")
+    if precision is not None and getattr(model, "compute_dtype", None) is not None:
+        have = "bfloat16" if model.compute_dtype == torch.bfloat16 else "float32"
+        if have != precision:
+            raise ValueError(f"the model computes in {have}; it cannot evaluate in {precision}")
+    metrics = metrics if metrics is not None else (M.evaluate_qa,)
+    qid_arr, logit_arr = [], []
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for data in batches:
+                logits = model(data, return_embeds=True)["logits"]
+                q, l = gather_qa_results(data["question_id"], logits)
+                qid_arr.append(q)
+                logit_arr.append(l)
+    finally:
+        model.train(was_training)
+    results = []
+    for q, l in zip(qid_arr, logit_arr):
+        for qid, pred in zip(q.tolist(), l.max(dim=-1)[1].tolist()):
+            results.append(dict(question_id=qid, answer=pred, data=qid2data[qid]))
+    nested = {fn.__name__: fn(results, label2ans, qid2data) for fn in metrics}
+    qids = torch.cat(qid_arr).numpy() if qid_arr else np.zeros(0, np.int64)
+    logits = torch.cat(logit_arr).numpy() if logit_arr else np.zeros((0, 0), np.float32)
+    return dict(results=results, question_ids=qids, logits=logits, preds=np.array([r["answer"] for r in results], np.int64), nested_val_metrics=nested)

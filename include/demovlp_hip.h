@@ -229,6 +229,51 @@ int dvlp_global_local_loss(int dtype, int64_t B, int64_t d, const void* gt, cons
 int dvlp_rownorm_fwd(int dtype, int64_t M, int64_t d, const void* x, float* xn, float* norm, void* stream);
 int dvlp_rownorm_bwd(int dtype, int64_t M, int64_t d, const void* x, const float* norm, const float* dxn, void* dx, void* stream);
 
+/* ---- video-QA answer head (csrc/qahead.hip): BUTDQAHead (model/video_qa_mdoel.py:56-97) on the embeddings ObjectQARelation.compute_fusion
+ *      hands over (model/model.py:281-289), and the QA loss (model/loss.py:180-187).  Every sum inside adds its partials in a fixed order. ---- */
+/* torch.nn.utils.weight_norm(nn.Linear, dim=None) (model/video_qa_mdoel.py:16-22, 63): W = g V / |V|_F with a scalar g, for `count` (<= 8)
+   tensors in one launch.  V, g, numel, W, Wb, dW, dV, dg are HOST arrays of `count` device pointers / element counts; everything they point to
+   is fp32 except Wb (optional bf16 copy of W; the table or single entries may be NULL).  norms [count] fp32 is written by _fwd and read by
+   _bwd, which turns the gradient dW of the folded weight into dV = (g / |V|) (dW - <dW, V> / |V|^2 V) and dg = <dW, V> / |V|. */
+int dvlp_wn_fold_fwd(int count, const void* const* V, const void* const* g, const int64_t* numel, void* const* W, void* const* Wb,
+                     float* norms, void* stream);
+int dvlp_wn_fold_bwd(int count, const void* const* V, const void* const* g, const int64_t* numel, const void* const* dW, const float* norms,
+                     void* const* dV, void* const* dg, void* stream);
+/* torch.max(text_embeddings, dim=1) (model/model.py:285): x [B][T][d] (dtype) -> out [B][d] fp32 and idx [B][d] int32, the FIRST maximal
+   token (padded tokens take part, as in the reference; unlike torch.max a NaN never wins the comparison, it is skipped); _bwd scatters dout [B][d] back into dx [B][T][d] (dtype), zero elsewhere */
+int dvlp_token_max_fwd(int dtype, int64_t B, int64_t T, int64_t d, const void* x, float* out, void* idx, void* stream);
+int dvlp_token_max_bwd(int dtype, int64_t B, int64_t T, int64_t d, const float* dout, const void* idx, void* dx, void* stream);
+/* Attention.forward + the weighted region sum of BUTDQAHead.forward (model/video_qa_mdoel.py:56-75, 94-97), widths fixed at 256.  Per sample b:
+     qp = relu(Wq q_b + bq);  H = v_b Wv^T + bv [G][256];  logit_g = ((relu(H_g) . qp . keep_g / (1 - drop_p)) . wl + bl) mask[b][g]
+     att = softmax_g(logit)  (the mask MULTIPLIES, so padded regions keep logit 0 and take part);  pooled = sum_g att_g v_g
+   v (dtype) is read in place: region g of sample b starts at v + b v_sample_stride + g v_row_stride (elements; 16-byte aligned, 256 contiguous
+   channels).  mask [B][G], q [B][256], Wq [256][256], bq, bv, wl [256], bl [1] are fp32 (the FOLDED weights).
+   Route: H == NULL is the fused one (dvlp_qa_attend_fused(dtype, G) != 0: bf16, G <= 288; anything else returns DVLP_ERR_UNSUPPORTED) -- Wv_bf16
+   [256][256] is staged in LDS, H is formed by v_mfma_f32_16x16x32_bf16 on a (64-row tile, sample) grid and consumed in registers.  Otherwise H
+   (dtype, row b hrows + g, 256 channels, bias added, before the ReLU) is the caller's dvlp_gemm product and Wv_bf16 is not read.
+   Dropout (drop_p > 0): keep bits are Philox words of drop_state at `site`, element (b G + g) 256 + n in the numbering of dvlp_dropout_fwd;
+   _fwd copies the four state words to state_snapshot, which is what _bwd takes.
+   Outputs: qp [B][256], att [B][G], pooled [B][256] fp32.
+   _bwd: from d_pooled [B][256] fp32 it writes dv (dtype, row b hrows + g: the direct part att_g d_pooled ONLY), dH (dtype, same rows: the
+   gradient of H before the ReLU; rows g >= G of a sample are not written), dq [B][256], dWq [256][256], dbq, dbv, dwl [256], dbl [1] fp32.  The
+   two large products are the caller's: dv += dH Wv (DVLP_EPI_ACCUM) and dWv = dH^T v.  The fused route recomputes H.  workspace: fp32,
+   dvlp_qa_attend_workspace_floats(B, G) elements. */
+int64_t dvlp_qa_attend_fused(int dtype, int64_t G);
+int64_t dvlp_qa_attend_workspace_floats(int64_t B, int64_t G);
+int dvlp_qa_attend_fwd(int dtype, int64_t B, int64_t G, const void* v, int64_t v_sample_stride, int64_t v_row_stride, const float* mask,
+                       const float* q, const float* Wq, const float* bq, const void* Wv_bf16, const float* bv, const float* wl, const float* bl,
+                       const void* H, int64_t hrows, float drop_p, const void* drop_state, int site, void* state_snapshot, float* qp, float* att,
+                       float* pooled, void* stream);
+int dvlp_qa_attend_bwd(int dtype, int64_t B, int64_t G, const void* v, int64_t v_sample_stride, int64_t v_row_stride, const float* mask,
+                       const float* q, const float* Wq, const void* Wv_bf16, const float* bv, const float* wl, const void* H, int64_t hrows,
+                       float drop_p, const void* state_snapshot, int site, const float* qp, const float* att, const float* d_pooled, void* dv,
+                       void* dH, float* dq, float* dWq, float* dbq, float* dbv, float* dwl, float* dbl, float* workspace, void* stream);
+/* nn.CrossEntropyLoss (model/loss.py:180-187) and the trainer's `logits.max(dim=-1)[1]` (trainer/trainer_dist.py:545) in one pass over fp32
+   logits [B][C] with int64 labels [B]: loss_rows [B], loss [1] = their mean (summed in row order), dlogits [B][C] = (softmax - onehot) / B
+   (NULL: not wanted), pred [B] int32 = first maximal class (a NaN logit never wins the arg-max, unlike torch.max).  A label outside [0, C) makes its row's loss NaN. */
+int dvlp_softmax_xent(int64_t B, int64_t C, const float* logits, const void* labels, float* loss_rows, float* dlogits, void* pred, float* loss,
+                      void* stream);
+
 /* ---- optimizer: transformers.AdamW as constructed at train_dist_multi.py:64 ---- */
 int dvlp_adamw_step(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int64_t step, float grad_scale, void* bf16_shadow, void* stream);
