@@ -1547,6 +1547,49 @@ extern "C" int dvlp_xattn_pairs_fwd(int dtype, int64_t Bi, int64_t Bj, int64_t K
     return DVLP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// resident video index (text-to-video search): the fused kernel's prepared video side kept by the caller, and the query-major pair list
+// over it -- scores[j][k] = local similarity of caption j and video cand[j K + k] of the index.  bf16, fused range only (xfused.hip).
+// ------------------------------------------------------------------------------------------------------------------
+int64_t dvlp_xfused_index_bytes(int64_t capacity, int64_t G);
+int64_t dvlp_xfused_query_bytes(int64_t Bj, int64_t W);
+int dvlp_xfused_index_add(int64_t capacity, int64_t G, int64_t row0, int64_t n, const void* Craw, void* index, hipStream_t st);
+int dvlp_xfused_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, const void* Qraw,
+                                const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores, void* workspace, hipStream_t st);
+
+extern "C" int64_t dvlp_xattn_index_bytes(int64_t capacity, int64_t G) {
+    if (capacity <= 0 || capacity > INT32_MAX || G <= 0) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, 112)) return DVLP_ERR_UNSUPPORTED;       // (with the longest caption the kernel takes: G <= 288)
+    return dvlp_xfused_index_bytes(capacity, G);
+}
+
+extern "C" int dvlp_xattn_index_add(int64_t capacity, int64_t G, int64_t row0, int64_t n, const void* Craw, void* index, void* stream) {
+    dvlp_clear_status();
+    if (capacity <= 0 || capacity > INT32_MAX || G <= 0 || row0 < 0 || n <= 0 || row0 + n > capacity) return DVLP_ERR_SHAPE;
+    if (!Craw || !index) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, 112)) return DVLP_ERR_UNSUPPORTED;       // (with the longest caption the kernel takes: G <= 288)
+    dvlp_xfused_index_add(capacity, G, row0, n, Craw, index, (hipStream_t)stream);
+    return dvlp_launch_status();
+}
+
+extern "C" int64_t dvlp_xattn_index_query_workspace_bytes(int64_t Bj, int64_t W) {
+    if (Bj <= 0 || W <= 0) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(1, W)) return DVLP_ERR_UNSUPPORTED;
+    return dvlp_xfused_query_bytes(Bj, W);
+}
+
+extern "C" int dvlp_xattn_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                          const void* Qraw, const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores,
+                                          void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != XD || capacity <= 0 || capacity > INT32_MAX || G <= 0 || Bj <= 0 || W <= 0 || K <= 0) return DVLP_ERR_SHAPE;
+    if (Bj > 65535 || Bj * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mimg || !Qraw || !mcap || !cand || !scores || !workspace) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    dvlp_xfused_index_pairs_fwd(capacity, G, index, mimg, Bj, W, Qraw, mcap, K, cand, lam, gate & 1, scores, workspace, (hipStream_t)stream);
+    return dvlp_launch_status();
+}
+
 // workspace must be the one dvlp_xattn_fwd(..., bwd=1) filled.  Outputs: dC [Bi][G][d], dQ [Bj][W][d] (compute dtype).
 extern "C" int dvlp_xattn_bwd(int dtype, int64_t Bi, int64_t Bj, int64_t G, int64_t W, int64_t d, const void* Craw, const void* Qraw,
                               const float* mimg, const float* mcap, float lam, int gate, const float* dscores, void* workspace,

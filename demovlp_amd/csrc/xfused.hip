@@ -30,7 +30,7 @@ struct FusedArgs {
     const float *nc, *nq;                      // |C_raw| [Bi][G], |Q_raw| [Bj][W]
     const float *mimg, *mcap;                  // additive masks [Bi][G], [Bj][W]
     float* scores;                             // [Bi][Bj]; pair form: [Bi][K]
-    const int* cand;                           // pair form: caption of pair (i, k) = cand[i K + k] (NULL: i K + k)
+    const int* cand;                           // pair form: caption of pair (i, k) = cand[i K + k] (NULL: i K + k); index form: video of pair (j, k) = cand[j K + k]
     int Bi, Bj, G, W, Gr, Gk, Wp, Wk, K;
     float lam;
     int gate;
@@ -498,6 +498,20 @@ __global__ __launch_bounds__(512) void xf_pairs_fwd_kernel(FusedArgs a) {
     xf_pair_score(a, smem, i, j, a.scores + o);
 }
 
+// resident index, query-major pair list: workgroup (k, j) -> scores[j][k], video cand[j K + k] of the index (a.Bi = its capacity); an index
+// outside [0, capacity) reads nothing and scores NaN (the -1 of a short top-k list lands here)
+__global__ __launch_bounds__(512) void xf_index_pairs_kernel(FusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int j = blockIdx.y;
+    const int64_t o = (int64_t)j * a.K + blockIdx.x;
+    const int i = a.cand[o];
+    if (i < 0 || i >= a.Bi) {
+        if (threadIdx.x == 0) a.scores[o] = __builtin_nanf("");
+        return;
+    }
+    xf_pair_score(a, smem, i, j, a.scores + o);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // host side (called from dvlp_xattn_fwd / dvlp_xattn_bwd in xattn.hip)
 // ------------------------------------------------------------------------------------------------------------------
@@ -565,5 +579,65 @@ int dvlp_xfused_pairs_fwd(int64_t Bi, int64_t Bj, int64_t K, int64_t G, int64_t 
     { static bool once = false; if (!once) { once = true;
         (void)hipFuncSetAttribute((const void*)xf_pairs_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
     hipLaunchKernelGGL(xf_pairs_fwd_kernel, dim3((unsigned)K, (unsigned)Bi), dim3(512), (size_t)L.total, st, a);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// resident video side (dvlp_xattn_index_*): the prepared form xf_prep writes per call -- chat [Gr][256], chatT [256][Gk] (bf16), nc [G]
+// (fp32) per video -- in caller-owned memory for `capacity` videos, filled `n` rows at a time by the same prep kernel (a row's bytes do not
+// depend on which call wrote it); a query call then preps its Bj captions only.
+// ------------------------------------------------------------------------------------------------------------------
+struct IndexLayout { int64_t Gr, Gk, off_chat, off_chatT, off_nc, total; };
+static IndexLayout index_layout(int64_t capacity, int64_t G) {
+    IndexLayout I{};
+    I.Gr = frup(G, 16); I.Gk = frup(G, 32);
+    I.off_chat = 0;
+    I.off_chatT = frup(capacity * I.Gr * FD * 2, 256);
+    I.off_nc = I.off_chatT + frup(capacity * FD * I.Gk * 2, 256);
+    I.total = I.off_nc + frup(capacity * G * 4, 256);
+    return I;
+}
+struct QueryLayout { int64_t Wp, Wk, off_qhat, off_qhatT, off_nq, total; };
+static QueryLayout query_layout(int64_t Bj, int64_t W) {
+    QueryLayout Q{};
+    Q.Wp = frup(W, 16); Q.Wk = frup(W, 32);
+    Q.off_qhat = 0;
+    Q.off_qhatT = frup(Bj * Q.Wp * FD * 2, 256);
+    Q.off_nq = Q.off_qhatT + frup(Bj * FD * Q.Wk * 2, 256);
+    Q.total = Q.off_nq + frup(Bj * W * 4, 256);
+    return Q;
+}
+
+int64_t dvlp_xfused_index_bytes(int64_t capacity, int64_t G) { return index_layout(capacity, G).total; }
+int64_t dvlp_xfused_query_bytes(int64_t Bj, int64_t W) { return query_layout(Bj, W).total; }
+
+int dvlp_xfused_index_add(int64_t capacity, int64_t G, int64_t row0, int64_t n, const void* Craw, void* index, hipStream_t st) {
+    const IndexLayout I = index_layout(capacity, G);
+    char* ix = (char*)index;
+    const int64_t rc = I.Gr > I.Gk ? I.Gr : I.Gk;
+    hipLaunchKernelGGL(xf_prep_kernel, dim3((unsigned)cdiv(n * rc, 4)), dim3(256), 0, st, (int)n, (int)G, (int)I.Gr, (int)I.Gk, (const bf16*)Craw,
+                       (bf16*)(ix + I.off_chat) + row0 * I.Gr * FD, (bf16*)(ix + I.off_chatT) + row0 * FD * I.Gk, (float*)(ix + I.off_nc) + row0 * G);
+    return 0;
+}
+
+int dvlp_xfused_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, const void* Qraw,
+                                const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores, void* workspace, hipStream_t st) {
+    const IndexLayout I = index_layout(capacity, G);
+    const QueryLayout Q = query_layout(Bj, W);
+    const char* ix = (const char*)index;
+    char* ws = (char*)workspace;
+    FusedArgs a{};
+    a.chat = (const bf16*)(ix + I.off_chat); a.chatT = (const bf16*)(ix + I.off_chatT); a.nc = (const float*)(ix + I.off_nc);
+    a.qhat = (const bf16*)(ws + Q.off_qhat); a.qhatT = (const bf16*)(ws + Q.off_qhatT); a.nq = (const float*)(ws + Q.off_nq);
+    a.mimg = mimg; a.mcap = mcap; a.scores = scores; a.cand = cand; a.K = (int)K;
+    a.Bi = (int)capacity; a.Bj = (int)Bj; a.G = (int)G; a.W = (int)W; a.Gr = (int)I.Gr; a.Gk = (int)I.Gk; a.Wp = (int)Q.Wp; a.Wk = (int)Q.Wk;
+    a.lam = lam; a.gate = gate; a.stop = g_xf_stop;
+    const int64_t rq = Q.Wp > Q.Wk ? Q.Wp : Q.Wk;
+    hipLaunchKernelGGL(xf_prep_kernel, dim3((unsigned)cdiv(Bj * rq, 4)), dim3(256), 0, st, (int)Bj, (int)W, (int)Q.Wp, (int)Q.Wk, (const bf16*)Qraw,
+                       (bf16*)(ws + Q.off_qhat), (bf16*)(ws + Q.off_qhatT), (float*)(ws + Q.off_nq));
+    const FLds L = flds(a.Gr, a.Gk, a.Wp, a.Wk);
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xf_index_pairs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xf_index_pairs_kernel, dim3((unsigned)K, (unsigned)Bj), dim3(512), (size_t)L.total, st, a);
     return 0;
 }

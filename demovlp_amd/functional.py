@@ -674,6 +674,20 @@ class XattnPairsFn(torch.autograd.Function):
         raise ops._lib.DemoVLPHipError("the pair-list local similarity (dvlp_xattn_pairs_fwd) is forward only: it has no backward")
 
 
+class XattnIndexPairsFn(torch.autograd.Function):
+    """xattn_score_fast of caption j against the videos cand[j, k] of a resident index (ops.xattn_index_add): [n_cap, K] scores.  Forward only
+    (search); a backward through it raises."""
+
+    @staticmethod
+    def forward(ctx, index, capacity, G, im_m, s, s_m, cand, lam, gate):
+        return ops.xattn_index_pairs_fwd(index, capacity, G, im_m.contiguous().float(), s.contiguous(), s_m.contiguous().float(),
+                                         cand.contiguous(), lam, gate)
+
+    @staticmethod
+    def backward(ctx, dscores):
+        raise ops._lib.DemoVLPHipError("the index pair-list local similarity (dvlp_xattn_index_pairs_fwd) is forward only: it has no backward")
+
+
 class RWATailFn(torch.autograd.Function):
     """model/loss.py:105-116 on a given score matrix."""
 

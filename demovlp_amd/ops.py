@@ -773,6 +773,73 @@ def xattn_pairs_fwd(C, Q, m_img, m_cap, cand, K, lam, gate):
     return scores
 
 
+def _size(name, *args):
+    n = call(name, *args)
+    if n < 0:
+        raise _lib.DemoVLPHipError(f"{name} failed: {_lib.ERRORS.get(int(n), n)}")
+    return int(n)
+
+
+def xattn_index_bytes(capacity, G):
+    """Bytes of the prepared (resident) video side of ``capacity`` videos with G regions each; raises outside the fused kernel's range."""
+    return _size("dvlp_xattn_index_bytes", int(capacity), int(G))
+
+
+def xattn_index_add(index, capacity, G, row0, C):
+    """Prepare the videos C (bf16 [n, G, 256]) into rows row0 .. row0 + n of ``index`` (uint8 [xattn_index_bytes(capacity, G)])."""
+    if C.dtype != torch.bfloat16:
+        raise _lib.DemoVLPHipError(f"the resident video index is bf16 only, got {C.dtype}")
+    if C.dim() != 3 or C.shape[1] != G or C.shape[2] != 256:
+        raise _lib.DemoVLPHipError(f"expected C [n, {G}, 256], got {tuple(C.shape)}")
+    if index.numel() * index.element_size() < xattn_index_bytes(capacity, G):
+        raise _lib.DemoVLPHipError("index buffer smaller than dvlp_xattn_index_bytes(capacity, G)")
+    require_gpu(index, C)
+    call("dvlp_xattn_index_add", int(capacity), int(G), int(row0), C.shape[0], p(C), p(index), stream())
+
+
+def xattn_index_pairs_fwd(index, capacity, G, m_img, Q, m_cap, cand, lam, gate):
+    """index: prepared videos (xattn_index_add), m_img fp32 [capacity, G]; Q bf16 [Bj, W, 256], m_cap fp32 [Bj, W]; cand int32 [Bj, K] video rows
+    -> scores fp32 [Bj, K] of the pairs (cand[j, k], j); an entry of cand outside [0, capacity) scores NaN.  Forward only."""
+    if Q.dtype != torch.bfloat16:
+        raise _lib.DemoVLPHipError(f"the resident video index is bf16 only, got {Q.dtype}")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != Q.shape[0]:
+        raise _lib.DemoVLPHipError(f"cand must be int32 [Bj, K], got {cand.dtype} {tuple(cand.shape)}")
+    if tuple(m_img.shape) != (capacity, G) or tuple(m_cap.shape) != tuple(Q.shape[:2]):
+        raise _lib.DemoVLPHipError(f"masks must be [capacity, G] and [Bj, W], got {tuple(m_img.shape)} and {tuple(m_cap.shape)}")
+    require_gpu(index, m_img, Q, m_cap, cand)
+    Bj, W, d = Q.shape
+    K = cand.shape[1]
+    ws = torch.empty(_size("dvlp_xattn_index_query_workspace_bytes", Bj, W), device=Q.device, dtype=torch.uint8)
+    scores = torch.empty((Bj, K), device=Q.device, dtype=torch.float32)
+    call("dvlp_xattn_index_pairs_fwd", int(capacity), int(G), p(index), p(m_img), Bj, W, d, p(Q), p(m_cap), K, p(cand), float(lam),
+         _gate_bits(gate) & 1, p(scores), p(ws), stream())
+    return scores
+
+
+def topk_rows(x, K, N=None, index_base=0, out=None, merge=False):
+    """x fp32 [M, ld] (first N columns; default all) -> (val fp32 [M, K], idx int32 [M, K]): per row the K largest values in descending order,
+    ties by smaller index (np.argsort(-x, kind="stable")[:, :K] + index_base), NaN last, (-inf, -1) where N < K.  ``out`` = (val, idx) to write
+    there; with ``merge`` their K entries take part as further candidates (streaming over column chunks)."""
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise _lib.DemoVLPHipError(f"topk_rows expects an fp32 matrix with unit column stride, got {x.dtype} {tuple(x.shape)}")
+    M, ld = x.shape[0], (x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1]))
+    N = x.shape[1] if N is None else int(N)
+    K = int(K)
+    if merge and out is None:
+        raise _lib.DemoVLPHipError("merge needs the (val, idx) of the earlier chunks in `out`")
+    if out is None:
+        out = (torch.empty((M, K), device=x.device, dtype=torch.float32), torch.empty((M, K), device=x.device, dtype=torch.int32))
+    val, idx = out
+    if (val.dtype, idx.dtype) != (torch.float32, torch.int32) or tuple(val.shape) != (M, K) or tuple(idx.shape) != (M, K) \
+            or not val.is_contiguous() or not idx.is_contiguous():
+        raise _lib.DemoVLPHipError("out must be contiguous (fp32 [M, K], int32 [M, K])")
+    nbytes = _size("dvlp_topk_workspace_bytes", M, N, K)
+    require_gpu(x, val, idx)
+    ws = torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
+    call("dvlp_topk_rows", M, N, p(x), ld, K, int(index_base), p(val), p(idx), int(bool(merge)), p(ws), stream())
+    return val, idx
+
+
 def global_local_loss(gt, go, xs, temperature, lam, use_global, use_local, stages, sim=None, dsim=None):
     """Raw call of the fused loss-head kernel.  Returns dict with whichever of sim/dsim/dgt/dgo/dxs/losses were produced."""
     ref = gt if gt is not None else (xs if xs is not None else sim)

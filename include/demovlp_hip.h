@@ -217,6 +217,36 @@ int dvlp_xattn_pairs_fwd(int dtype, int64_t Bi, int64_t Bj, int64_t K, int64_t G
                          const float* mimg, const float* mcap, const int* cand, float lam, int gate, float* scores, void* workspace,
                          void* stream);
 
+/* Resident video index + query-major pair list (text-to-video search, demovlp_amd/search.py): the local similarity above
+   (model/loss.py:209-330) of caption j against the videos cand[j K + k] of a collection whose video side was prepared ONCE.
+   The index is caller-owned device memory of dvlp_xattn_index_bytes(capacity, G) bytes holding, per video, what the fused kernel's prep
+   writes per call (normalised regions in both orientations, bf16, and the region norms, fp32: ~296 KB at G = 288).  bf16 only and only inside
+   the fused kernel's range (G <= 288, W <= 112): anything else returns DVLP_ERR_UNSUPPORTED (size helpers: as a negative value).
+     dvlp_xattn_index_add        preps videos Craw (bf16 [n][G][256]) into rows row0 .. row0 + n; a row's bytes do not depend on the call
+                                 that wrote it (several adds == one add).  No reference counterpart.
+     dvlp_xattn_index_pairs_fwd  preps the Bj captions Qraw (bf16 [Bj][W][256]) into `workspace` (dvlp_xattn_index_query_workspace_bytes(Bj, W):
+                                 independent of the capacity), then one workgroup per (k, j) runs the per-pair code of the full-grid fused
+                                 kernel: scores[j][k] (fp32 [Bj][K]) equals entry [cand[j K + k]][j] of dvlp_xattn_fwd's grid bit for bit.  cand is
+                                 int32 [Bj][K] on the device; an entry outside [0, capacity) reads nothing and scores NaN (the -1 of a short
+                                 dvlp_topk_rows list).  mimg is the additive region mask of the whole index, fp32 [capacity][G].  Bj <= 65535. */
+int64_t dvlp_xattn_index_bytes(int64_t capacity, int64_t G);
+int dvlp_xattn_index_add(int64_t capacity, int64_t G, int64_t row0, int64_t n, const void* Craw, void* index, void* stream);
+int64_t dvlp_xattn_index_query_workspace_bytes(int64_t Bj, int64_t W);
+int dvlp_xattn_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                               const void* Qraw, const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores,
+                               void* workspace, void* stream);
+
+/* ---- row top-k (csrc/topk.hip; no reference counterpart: the reference ranks on the host, model/metric.py) ----
+   Per row m of the fp32 matrix x [M][ld] (first N columns): val[m][0..K) = the K largest values, descending, idx[m][..] = their column numbers
+   + index_base (int32).  Total order: larger value first, equal values by smaller index -- np.argsort(-x, kind="stable")[:K]; -0.0 == +0.0; a NaN
+   sorts after every number.  N < K: the tail is val = -inf, idx = -1.  merge = 1: the K entries already in val / idx take part as further
+   candidates (idx as they are; idx < 0 = filler), so a caller can stream over column chunks (index_base = c * chunk, merge = c > 0) and gets
+   the one-shot result bit for bit.  Values come back with the bits they had.  No float atomics; the result does not depend on scheduling.
+   1 <= K <= 1024, N < 2^31, ld >= N, index_base + N < 2^31; workspace: dvlp_topk_workspace_bytes(M, N, K) (negative DVLP_ERR_* for a bad shape). */
+int64_t dvlp_topk_workspace_bytes(int64_t M, int64_t N, int K);
+int dvlp_topk_rows(int64_t M, int64_t N, const float* x, int64_t ld, int K, int64_t index_base, float* val, int* idx, int merge,
+                   void* workspace, void* stream);
+
 /* ---- loss heads: sim_matrix (model/model.py:582-590) + NormSoftmaxLoss (model/loss.py:126-138) + RWALoss tail
  *      (model/loss.py:105-116) + GlobalLocalLoss sum (:29-45); forward and analytic gradients in one launch        ---- */
 int dvlp_global_local_loss(int dtype, int64_t B, int64_t d, const void* gt, const void* go, const float* xs, float temperature,
