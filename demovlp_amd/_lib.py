@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The product library exports no developer switch (`dvlp_dev_*`); the same sources built with -DDVLP_DEV are libdemovlp_hip_dev.so
@@ -50,6 +51,7 @@ _RET64 = {n for n, (r, _) in {**_SIGS, **_DEV_SIGS}.items() if r is ctypes.c_int
 
 _libs = {}             # path -> (CDLL, has developer switches)
 _active = LIB_PATH
+_py_switches = {}      # "dvlp_dev_<name>" -> (module, attribute): developer switches that live in a Python module, behind the same door as the C ones
 _switch_hooks = []     # called with the OLD library still active, before another one takes over (ops drops what it registered there)
 
 
@@ -113,12 +115,22 @@ def exported_symbols(dev=False):
     return list(_DEV_SIGS if dev else _SIGS)
 
 
+def register_switch(name, module, attr):
+    """``call("dvlp_dev_<name>", int)`` sets the boolean ``attr`` of ``module`` -- under the guard of every developer switch: refused unless the
+    developer library is active.  Nothing else writes these attributes; the environment is not read."""
+    _py_switches["dvlp_dev_" + name] = (module, attr)
+
+
 def call(name, *args):
     """Invoke an entry point; raise on a non-zero status."""
     lib = load()
     if name.startswith("dvlp_dev_") and not _libs[_active][1]:
         raise DemoVLPHipError(f"{name} is a developer switch: the product library does not export it -- "
                               f"demovlp_amd._lib.use_dev_library() switches to {os.path.basename(DEV_LIB_PATH)}")
+    if name in _py_switches:
+        module, attr = _py_switches[name]
+        setattr(sys.modules[module], attr, bool(args[0]))
+        return 0
     fn = getattr(lib, name)
     rc = fn(*args)
     if name in _RET64:

@@ -12,6 +12,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdemovlp_hip.so")
 DEV_LIB = os.path.join(LIBDIR, "libdemovlp_hip_dev.so")      # the same sources under -DDVLP_DEV: exports the dvlp_dev_* switches (tests, tools)
 SOURCES = ["gemm.hip", "gemm_rb.hip", "norm.hip", "attention.hip", "embed.hip", "xattn.hip", "xfused.hip", "losses.hip", "select.hip", "topk.hip", "optim.hip", "dropout.hip", "qahead.hip"]
+HEADERS = ["common.h", "gemm_plan.h"]      # every object is rebuilt when one of them changes
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 
 
@@ -33,7 +34,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = True) -> str:
     """Product library (no developer switch exported) and, with ``dev``, libdemovlp_hip_dev.so beside it."""
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
-    hdr = os.path.join(CSRC, "common.h")
+    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     variants = [("", [], LIB)] + ([("_dev", ["-DDVLP_DEV"], DEV_LIB)] if dev else [])
     jobs, links = [], []
     for suffix, defs, lib in variants:
@@ -42,7 +43,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = True) -> str:
             src = os.path.join(CSRC, s)
             obj = os.path.join(LIBDIR, s.replace(".hip", suffix + ".o"))
             objs.append(obj)
-            if force or _stale(obj, [src, hdr]):
+            if force or _stale(obj, [src, *hdrs]):
                 jobs.append([hipcc, *FLAGS, *defs, "-c", src, "-o", obj])
         links.append((lib, objs))
 
@@ -70,7 +71,7 @@ def build_stamp(verbose: bool = True) -> str:
     obj = os.path.join(LIBDIR, "gemm_stamp.o")
     src = os.path.join(CSRC, "gemm.hip")
     objs = [os.path.join(LIBDIR, s.replace(".hip", "_dev.o")) for s in SOURCES if s != "gemm.hip"] + [obj]
-    if _stale(obj, [src, os.path.join(CSRC, "common.h")]):
+    if _stale(obj, [src, *(os.path.join(CSRC, h) for h in HEADERS)]):
         subprocess.run([hipcc, *FLAGS, "-DDVLP_STAMP", "-DDVLP_DEV", "-c", src, "-o", obj], check=True)
     if _stale(out, objs):
         subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *objs], check=True)

@@ -1452,33 +1452,30 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(int64_t M, int64_t N
 int g_dvlp_last_hip_error = 0;
 extern "C" const char* dvlp_last_error_string() { return hipGetErrorString((hipError_t)g_dvlp_last_hip_error); }
 
-// A/B switch between the LDS-DMA kernel (default) and the register-staged one (tools/gemm_bench.py --variant)
-static int g_ablate = 0;         // tools/gemm_bench.py --ablate: 1 skip LDS-DMA issue, 2 skip LDS fragment reads, 4 skip MFMAs (TIMING ONLY)
-DVLP_DEV_API int dvlp_dev_gemm_ablate(int bits) { g_ablate = bits; return DVLP_OK; }
-static bool g_use_glds = true;
-static int g_wide_mode = 0;      // 0: never use the 256-row tile (default: measured no faster on this path's shapes), 1: heuristic, 2: always
-DVLP_DEV_API int dvlp_dev_gemm_wide_mode(int mode) { g_wide_mode = mode; return DVLP_OK; }
-static int g_wgrad_ride = 1;     // grouped weight gradients: 1 = an optimizer update handed to dvlp_wgrad_grouped_ex rides on the launch's spare workgroups, 0 = its own launch
-DVLP_DEV_API int dvlp_dev_wgrad_group_ride(int on) { g_wgrad_ride = on; return DVLP_OK; }
-static int g_wgrad_patch = 1;    // grouped weight gradients: 1 = 3 x 3 tile patches pinned to XCDs (operand panels shared through L2), 0 = per-problem tile order
-DVLP_DEV_API int dvlp_dev_wgrad_group_patches(int on) { g_wgrad_patch = on; return DVLP_OK; }
-static int g_p8_mode = 1;        // 256 x 256 ping-pong kernel: 0 never, 1 where the grid suits it, 2 whenever the operands allow
-DVLP_DEV_API int dvlp_dev_gemm_p8_mode(int mode) { g_p8_mode = mode; return DVLP_OK; }
-static int g_p8_persist = 1;     // persistent form of the 256-row kernel on multi-round outputs: 0 off, 1 on (default; A/B: tools/p8p_bench.py)
-DVLP_DEV_API int dvlp_dev_gemm_p8_persistent(int mode) { g_p8_persist = mode; return DVLP_OK; }
-static int g_rb = 1;             // resident-B streaming kernel (csrc/gemm_rb.hip) for batched skinny products: 0 never, 1 where its shapes fit (default)
-DVLP_DEV_API int dvlp_dev_gemm_resident_b(int on) { g_rb = on; return DVLP_OK; }
+// Developer switches (defaults and meaning: GemmKnobs in gemm_plan.h); each setter writes one field
+#include "gemm_plan.h"
+static_assert(gp::F32 == DVLP_F32 && gp::BF16 == DVLP_BF16 && gp::ERR_DTYPE == DVLP_ERR_DTYPE && gp::ERR_SHAPE == DVLP_ERR_SHAPE, "gemm_plan.h mirrors common.h");
+static_assert(gp::GELU == EPI_GELU && gp::GELU_BWD == EPI_GELU_BWD && gp::RELU_BWD == EPI_RELU_BWD && gp::ACCUM == EPI_ACCUM && gp::OUT_F32 == EPI_OUT_F32, "gemm_plan.h mirrors common.h");
+static_assert(gp::BM == F_BM && gp::BN == F_BN && gp::BM == H_BM && gp::BN == H_BN && gp::BK == H_BK && gp::EK_ANY == P8_EK_ANY, "gemm_plan.h mirrors the tile constants");
+static_assert(gp::LDS_128 == 4 * H_TILE * sizeof(bf16) && gp::LDS_P8 == P_LDS_TOTAL, "gemm_plan.h mirrors the LDS sizes");
+static_assert(4 * 64 * 68 * sizeof(float) <= (size_t)4 * H_TILE * sizeof(bf16), "epilogue staging must fit the K-loop buffers");
+static GemmKnobs g_knobs;
+DVLP_DEV_API int dvlp_dev_gemm_ablate(int bits) { g_knobs.ablate = bits; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_variant(int use_lds_dma) { g_knobs.use_glds = use_lds_dma != 0; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_wide_mode(int mode) { g_knobs.wide_mode = mode; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_p8_mode(int mode) { g_knobs.p8_mode = mode; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_p8_short_tiles(int mode) { g_knobs.p8_short = mode; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_p8_persistent(int mode) { g_knobs.p8_persist = mode; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_resident_b(int on) { g_knobs.rb = on; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_force_split(int s) { g_knobs.force_split = s; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_splitk_target(int64_t n) { g_knobs.splitk_target = n > 0 ? n : 768; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_gemm_corun_split(int on) { g_knobs.corun_split = on; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_wgrad_group_ride(int on) { g_knobs.wgrad_ride = on; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_wgrad_group_patches(int on) { g_knobs.wgrad_patch = on; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_wgrad_group_split(int s) { g_knobs.wgrad_split = s; return DVLP_OK; }
+DVLP_DEV_API int dvlp_dev_wgrad_corun_split(int on) { g_knobs.corun_wgrad_split = on; return DVLP_OK; }
 bool dvlp_gemm_rb_try(int transA, int transB, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
                       int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, hipStream_t st);
-static int g_p8_short = 1;       // 224-row tiles of the 256-row kernel: 0 never, 1 where they save CU-rounds (default), 2 whenever allowed
-DVLP_DEV_API int dvlp_dev_gemm_p8_short_tiles(int mode) { g_p8_short = mode; return DVLP_OK; }
-static int g_force_split = 0;    // dvlp_gemm: 0 = automatic K split, > 0 = forced (A/B measurements: tools/gemm_sweep.py)
-DVLP_DEV_API int dvlp_dev_gemm_force_split(int s) { g_force_split = s; return DVLP_OK; }
-static int g_wgrad_split = 0;    // grouped weight gradients: 0 = automatic uniform K split, > 0 = forced
-DVLP_DEV_API int dvlp_dev_wgrad_group_split(int s) { g_wgrad_split = s; return DVLP_OK; }
-static int64_t g_splitk_target = 768;     // workgroups a split-K launch aims for (tools/gemm_bench.py --splitk-target)
-DVLP_DEV_API int dvlp_dev_gemm_splitk_target(int64_t n) { g_splitk_target = n > 0 ? n : 768; return DVLP_OK; }
-DVLP_DEV_API int dvlp_dev_gemm_variant(int use_lds_dma) { g_use_glds = use_lds_dma != 0; return DVLP_OK; }
 
 // caller-provided scratch for split-K slabs (dvlp_set_workspace); nullptr disables splitting
 // One scratch buffer per stream (two GEMMs in flight on different streams must not share slabs); stream 0 entry is the
@@ -1577,29 +1574,16 @@ struct dvlp_gemm_ext {
     int colsum_fused;       // out: 1 = queued from inside the GEMM's epilogue (final after the deferred reductions are flushed), 0 = a plain pass ran
 };
 
-// Tile height x K split of the 256-column kernel for an under-filled or round-quantised output (round 6).  What a block costs is not
-// proportional to its rows: per 64-deep K tile ~ (0.55 + 0.0016 rows) us on a lightly filled chip, up to ~1.35x that when every CU streams
-// (clock and L2 share), plus a prologue + epilogue of ~ (6 + 0.028 rows) us; a K split adds the slab round trip and the reduction launch
-// (~2.5 us + 1.08 us per million output elements and slice).  Constants fitted to tools/tile_sweep.py on MI355X (profiles/r6_tile_sweep.txt:
-// M = 6400 / 7712 / 18496 tokens x the eight forward / dX shapes of a layer); the model only has to RANK the candidates.
-struct P8Plan { int mih; int64_t S; };
-static P8Plan p8_plan(int64_t M, int64_t N, int64_t K, int64_t ntn8, int ncu, bool may_split, int64_t ws_bytes) {
-    const int64_t nk = K / 64;
-    P8Plan best{4, 1};
-    double best_c = 1e30;
-    for (int h = 4; h >= 1; --h) {
-        const int64_t rows = 128 + 32 * h, nb1 = cdiv(M, rows) * ntn8;
-        for (int64_t S = 1; S <= (may_split ? 4 : 1); ++S) {
-            if (S > 1 && (nk < 8 * S || nb1 >= 200 || S * M * N * 4 > ws_bytes)) break;
-            const int64_t nb = nb1 * S, rounds = cdiv(nb, ncu);
-            const double fill = (double)nb / (double)(rounds * ncu);
-            const double crowd = 1.0 + 0.35 * (fill > 0.3 ? (fill - 0.3) / 0.7 : 0.0);
-            const double tk = (0.55 + 0.0016 * rows) * crowd, fixed = 6.0 + 0.028 * rows;
-            const double c = rounds * ((double)cdiv(nk, S) * tk + fixed) + (S > 1 ? 2.5 + 1.08e-6 * (double)S * (double)M * (double)N : 0.0);
-            if (c < best_c * 0.995) { best_c = c; best = P8Plan{h, S}; }        // (ties go to the taller tile / the smaller split: tried first)
-        }
-    }
-    return best;
+static int cu_count() {
+    static const int ncu = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
+    return ncu;
+}
+static bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+// Everything gemm_plan needs that is looked up rather than passed: the stream's split-K workspace and hint, the CU count, the switches.
+static GemmPlan plan_for(const GemmProblem& p, void* stream, bool rd_queue = true) {
+    const WsEntry ws = ws_for(stream);
+    return gemm_plan(p, g_knobs, ws.ptr ? ws.bytes : 0, cu_count(), stream_co_running(stream), rd_queue);
 }
 
 static int gemm_batched_impl(int dtype, int transA, int transB, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
@@ -1609,177 +1593,66 @@ static int gemm_batched_impl(int dtype, int transA, int transB, int64_t M, int64
     dvlp_clear_status();
     float* const csum_dst = ext ? ext->colsum : nullptr;      // column sums of this GEMM's output requested
     if (ext) ext->colsum_fused = 0;
-    bool csum_fused = false;
-    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch > 65535) return DVLP_ERR_SHAPE;
-    if ((flags & (EPI_GELU | EPI_GELU_BWD | EPI_RELU_BWD)) && !aux) return DVLP_ERR_SHAPE;
+    const GemmProblem pb{dtype, transA, transB, M, N, K, lda, ldb, ldc, ldres, ldaux, batch, strideA, strideB, strideC, strideRes, strideAux, flags, alpha,
+                         bias != nullptr, res != nullptr, aux != nullptr, csum_dst != nullptr, al16(A), al16(B), al16(C), al16(res), al16(aux), al16(bias)};
+    GemmPlan pl = plan_for(pb, stream);
+    if (pl.err) return pl.err;
     hipStream_t st = (hipStream_t)stream;
-    Epi e{bias, res, aux, ldres, ldaux, flags | (g_ablate << 24), alpha, strideA, strideB, strideC, strideRes, strideAux, 0, nullptr};
-    {
-        const int64_t cal = (flags & EPI_OUT_F32) ? 4 : 8;      // elements per 16 bytes of C
-        bool v = (ldc % cal == 0) && ((uintptr_t)C % 16 == 0) && (strideC % cal == 0);
-        if (res) v = v && (ldres % 8 == 0) && ((uintptr_t)res % 16 == 0) && (strideRes % 8 == 0);
-        if (aux) v = v && (ldaux % 8 == 0) && ((uintptr_t)aux % 16 == 0) && (strideAux % 8 == 0);
-        if (bias) v = v && ((uintptr_t)bias % 16 == 0);
-        e.vec = v ? 1 : 0;
+    Epi e{bias, res, aux, ldres, ldaux, flags | (g_knobs.ablate << 24), alpha, strideA, strideB, strideC, strideRes, strideAux, pl.vec ? 1 : 0, nullptr};
+    if (pl.csum_fuse) {
+        e.csum = dvlp_rd_reserve_push(pl.csum_rows, N, csum_dst);
+        if (!e.csum) pl = plan_for(pb, stream, false);         // no room in the deferred-reduction queue: a plain pass below
     }
     ProfRec rec{};
     if (g_prof) {
         (void)hipEventCreate(&rec.a); (void)hipEventCreate(&rec.b);
-        rec.flops = 2.0 * M * N * K * batch; rec.M = M; rec.N = N; rec.K = K; rec.batch = batch; rec.form = transA * 2 + transB; rec.flags = flags; rec.kern = 0;
+        rec.flops = 2.0 * M * N * K * batch; rec.M = M; rec.N = N; rec.K = K; rec.batch = batch; rec.form = transA * 2 + transB; rec.flags = flags;
+        rec.kern = pl.family == GEMM_RB ? 4 : pl.family == GEMM_P8 ? 2 : pl.family == GEMM_DMA128 || pl.family == GEMM_WIDE ? 1 : 0;
         (void)hipEventRecord(rec.a, st);
     }
-    if (dtype == DVLP_F32) {
-        const int64_t ntm = cdiv(M, F_BM), ntn = cdiv(N, F_BN);
-        const int a_vec = (lda % 4 == 0) && ((uintptr_t)A % 16 == 0) && (strideA % 4 == 0);
-        const int b_vec = (ldb % 4 == 0) && ((uintptr_t)B % 16 == 0) && (strideB % 4 == 0);
-        dim3 grid((unsigned)(ntm * ntn), (unsigned)batch), block(256);
-#define LAUNCH_F32(AR, BR) hipLaunchKernelGGL((gemm_f32_kernel<AR, BR>), grid, block, 0, st, M, N, K, (const float*)A, lda, \
-                                              (const float*)B, ldb, (float*)C, ldc, e, a_vec, b_vec, ntn)
-        if (!transA && !transB) LAUNCH_F32(false, false);
-        else if (!transA && transB) LAUNCH_F32(false, true);
-        else if (transA && transB) LAUNCH_F32(true, true);
-        else LAUNCH_F32(true, false);
-#undef LAUNCH_F32
-    } else if (dtype == DVLP_BF16 && g_rb && !bias && !res && !aux && flags == 0 && alpha == 1.0f && !csum_dst && !g_ablate &&
-               dvlp_gemm_rb_try(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, batch, strideA, strideB, strideC, st)) {
-        rec.kern = 4;             // batched skinny product with its B operand resident in LDS (the local loss' per-video / per-caption contractions)
-    } else if (dtype == DVLP_BF16) {
-        // 16-byte vector loads need 8-element-aligned leading dims and base pointers
-        if (lda % 8 || ldb % 8 || (uintptr_t)A % 16 || (uintptr_t)B % 16 || strideA % 8 || strideB % 8) return DVLP_ERR_SHAPE;
-        const int64_t ntm = cdiv(M, H_BM), ntn = cdiv(N, H_BN);
-        const size_t lds = (size_t)4 * H_TILE * sizeof(bf16);
-        static_assert(4 * 64 * 68 * sizeof(float) <= (size_t)4 * H_TILE * sizeof(bf16), "epilogue staging must fit the K-loop buffers");
-        // the branch-free loader clamps rows: form-K operands need >= 1 row, form-R operands a row count that is a multiple of 8
-        const bool safe = (transA ? (M % 8 != 0 || M < 8) : false) || (transB ? (N % 8 != 0 || N < 8) : false) || K < 8 || K % 8 != 0;
-        const bool dma = !safe && g_use_glds;                 // (!safe implies K % 8 == 0; a ragged last K tile is zero-filled)
-        // 256 x 256 ping-pong kernel: one workgroup per CU, so it wants >= ~a chip of tiles (or a K long enough to split)
-        const int64_t ntm8 = cdiv(M, 256), ntn8 = cdiv(N, 256), tiles8 = ntm8 * ntn8 * batch;
-        // ... and outputs that fill its tiles: 288 columns would leave the second 256-wide tile 7/8 empty
-        const bool fills8 = 10 * M * N >= 8 * (ntm8 * 256) * (ntn8 * 256);
-        // ... and a tile count that fills whole rounds of the 256 CUs (300 tiles = 2 rounds for 1.17 rounds of work); a long K
-        // (>= 32 K tiles) amortises its fixed costs well enough to win even at 75 tiles
-        const bool rounds8 = 10 * tiles8 >= 8 * 256 * cdiv(tiles8, 256);
-        // (measured per shape with tools/gemm_sweep.py: 75-tile outputs with K = 2304 / 3072 -- the text tower's fc2, fc1 dX, qkv dX -- run
-        //  faster on the 128-row kernel without a K split than on a 3-way split 256-row launch (47 vs 55, 38 vs 50, 48 vs 55 us), and a
-        //  3-tile weight gradient -- the two 256-wide projections -- on 384 128-row blocks than on 96 256-row ones)
-        // (round 3, in the step: with the text tower beside the object tower, its 75 / 300-tile products on the 256-row kernel -- any round
-        //  count -- take 1 % off the step; alone they measured slower, above.  DVLP_P8_MIN_TILES=192 DVLP_P8_ROUNDS=1 restores round 2's rule)
-        static const int p8_min_tiles = getenv("DVLP_P8_MIN_TILES") ? atoi(getenv("DVLP_P8_MIN_TILES")) : 64;      // experiments (round 3: 192 -> 64, see below)
-        static const bool p8_need_rounds = getenv("DVLP_P8_ROUNDS") ? atoi(getenv("DVLP_P8_ROUNDS")) != 0 : false;
-        // (round 6: batched long-K reductions whose output half-fills its tiles -- the local loss' dC^_i [288 x 256] and dQ^_j [104 x 256] products
-        //  over K = 6 656 / 18 432, batch 64 -- also run faster here with a 2- / 4-way K split than on the 128-row kernel: 181 -> 132, 162 -> 122,
-        //  197 -> 160 us (profiles/r6_loss_reductions_on_p8.txt); a [104 x 104] output does not: 108 -> 132)
-        const bool longk8 = batch >= 8 && K >= 4096 && N % 256 == 0 && 10 * M >= 4 * ntm8 * 256;
-        const bool p8 = dma && K % H_BK == 0 && g_p8_mode != 0 && (g_p8_mode == 2 || longk8 || (M >= 256 && N >= 256 && fills8 && ((tiles8 >= p8_min_tiles && (rounds8 || !p8_need_rounds)) || (tiles8 >= 8 && tiles8 <= 64 && K >= 4096))));
-        // Under-filled grids with a long reduction (weight gradients: 36-144 output tiles, K = B*N tokens) are split along
-        // K so that ~3 workgroups (128-row kernel) or 1 workgroup (256-row kernel) land on every CU; partials go through fp32
-        // slabs (deterministic, no float atomics).
-        int64_t S = 1;
-        const int64_t tiles = p8 ? tiles8 : ntm * ntn * batch;
-        const WsEntry wse = ws_for(stream);
-        float* g_ws = wse.ptr;
-        const int64_t g_ws_bytes = wse.bytes;
-        static const int ncu8 = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
-        // tile height (p8_tile_rows) and K split of the 256-column kernel, chosen TOGETHER where every tile takes a whole-tile store (row-major
-        // A, whole 256-column tiles, aligned outputs; a split launch writes slabs, which any height can): p8_plan above.  M = 18496: 224-row
-        // tiles (83 x {3, 9, 12} = 249 / 747 / 996 blocks fill 1 / 3 / 4 rounds of 256 CUs that 256-row tiles leave 14 % empty); M = 6400
-        // (the text tower): 160-row tiles (120 / 480 blocks instead of 75 / 300), K >= 2304 as 160 rows x 2 slices instead of 256 x 3.
-        int mih8 = 4;
-        const bool plan8 = p8 && g_p8_short != 0 && !transA && batch == 1 && N % 256 == 0 && e.vec && (N & 3) == 0;
-        const bool co_run = plan8 && g_p8_short == 1 && stream_co_running(stream);
-        if (plan8 && g_p8_short == 1 && g_force_split == 0 && !co_run) {
-            const P8Plan pl = p8_plan(M, N, K, ntn8, ncu8, g_ws != nullptr && K >= 1024, g_ws_bytes);
-            mih8 = pl.mih; S = pl.S;
-        } else {
-            // (a co-running launch is not split: slabs and a reduction launch buy latency it does not need with CU-time the other stream does --
-            //  DVLP_CORUN_SPLIT=1 restores the split for A/B runs)
-            static const bool corun_split = getenv("DVLP_CORUN_SPLIT") && atoi(getenv("DVLP_CORUN_SPLIT")) != 0;
-            if (g_ws && tiles < (p8 ? 129 : 200) && K >= 1024 && !(co_run && !corun_split)) {
-                S = p8 ? 256 / tiles : (g_splitk_target + tiles - 1) / tiles;
-                if (S > K / 256) S = K / 256;
-                if (S > 32) S = 32;
-                while (S > 1 && S * batch * M * N * 4 > g_ws_bytes) --S;
-            }
-            if (g_force_split > 0 && g_ws) { S = g_force_split; while (S > 1 && S * batch * M * N * 4 > g_ws_bytes) --S; }
-            if (plan8) {           // developer switches: a forced height (10 + MIH), "224 wherever allowed" (2), round 5's rule (3)
-                if (g_p8_short >= 10) mih8 = g_p8_short - 10 >= 1 && g_p8_short - 10 <= 4 ? g_p8_short - 10 : 4;
-                else if (g_p8_short == 2) mih8 = 3;
-                else if ((g_p8_short == 3 || co_run) && S == 1 && cdiv(cdiv(M, 224) * ntn8, ncu8) * 224 < cdiv(tiles8, ncu8) * 256) mih8 = 3;
-            }
-        }
-        int64_t kchunk = cdiv(cdiv(K, S), H_BK) * H_BK;
-        S = cdiv(K, kchunk);
-        float* slab = S > 1 ? g_ws : nullptr;
-        dim3 grid((unsigned)(ntm * ntn), (unsigned)batch, (unsigned)S), block(256);
-        // > 64 KiB of dynamic LDS must be opted into once per kernel
-#define LAUNCH_BF16_(AR, BR, SF) do { static bool once = false; if (!once) { once = true; \
-            (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<AR, BR, SF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); } \
-        hipLaunchKernelGGL((gemm_bf16_kernel<AR, BR, SF>), grid, block, lds, st, M, N, K, (const bf16*)A, lda, \
-                           (const bf16*)B, ldb, (bf16*)C, ldc, e, ntn, kchunk, slab); } while (0)
-#define LAUNCH_P8K_(AR, BR, EK, MIH) do { static bool once = false; if (!once) { once = true; \
-            (void)hipFuncSetAttribute((const void*)gemm_bf16_p8_kernel<AR, BR, EK, MIH>, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_TOTAL); } \
-        hipLaunchKernelGGL((gemm_bf16_p8_kernel<AR, BR, EK, MIH>), grid8, dim3(512), (size_t)P_LDS_TOTAL, st, M, N, K, (const bf16*)A, lda, \
-                           (const bf16*)B, ldb, (bf16*)C, ldc, e, ntn8, kchunk, slab); } while (0)
-#define LAUNCH_P8P_(AR, BR, EK, MIH) do { static bool once = false; if (!once) { once = true; \
-            (void)hipFuncSetAttribute((const void*)gemm_bf16_p8p_kernel<AR, BR, EK, MIH>, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_TOTAL); } \
-        hipLaunchKernelGGL((gemm_bf16_p8p_kernel<AR, BR, EK, MIH>), dim3((unsigned)ncu8), dim3(512), (size_t)P_LDS_TOTAL, st, M, N, K, (const bf16*)A, lda, \
-                           (const bf16*)B, ldb, (bf16*)C, ldc, e, (int)ntm8h, (int)ntn8); } while (0)
-#define LAUNCH_P8S_(AR, BR, EK) do { if constexpr (!AR && (EK == 0 || EK == 2)) { if (p8p) { LAUNCH_P8P_(AR, BR, EK, 3); break; } } if constexpr (!AR) { \
-        if (mih8 == 3) { LAUNCH_P8K_(AR, BR, EK, 3); break; } if (mih8 == 2) { LAUNCH_P8K_(AR, BR, EK, 2); break; } if (mih8 == 1) { LAUNCH_P8K_(AR, BR, EK, 1); break; } } \
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);
+    const int ntn = (int)pl.ntn, ntm = (int)pl.ntm;
+    const int64_t kchunk = pl.kchunk;
+    float* const slab = pl.S > 1 ? ws_for(stream).ptr : nullptr;
+    // The ladders below only map plan fields to template instantiations.  (> 64 KiB of dynamic LDS must be opted into once per kernel.)
+#define LAUNCH_(KERN, ...) do { static bool once = false; if (!once) { once = true; \
+            (void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds); } \
+        hipLaunchKernelGGL(KERN, grid, block, (size_t)pl.lds, st, M, N, K, (const bf16*)A, lda, (const bf16*)B, ldb, (bf16*)C, ldc, e, __VA_ARGS__); } while (0)
+#define LAUNCH_P8K_(AR, BR, EK, MIH) LAUNCH_((gemm_bf16_p8_kernel<AR, BR, EK, MIH>), ntn, kchunk, slab)
+#define LAUNCH_P8S_(AR, BR, EK) do { if constexpr (!AR && (EK == 0 || EK == 2)) { if (pl.p8p) { LAUNCH_((gemm_bf16_p8p_kernel<AR, BR, EK, 3>), ntm, ntn); break; } } \
+        if constexpr (!AR) { if (pl.mih8 == 3) { LAUNCH_P8K_(AR, BR, EK, 3); break; } if (pl.mih8 == 2) { LAUNCH_P8K_(AR, BR, EK, 2); break; } \
+                             if (pl.mih8 == 1) { LAUNCH_P8K_(AR, BR, EK, 1); break; } } \
         LAUNCH_P8K_(AR, BR, EK, 4); } while (0)
-#define LAUNCH_P8_(AR, BR) do { if (ek8 == 0) LAUNCH_P8S_(AR, BR, 0); else if (ek8 == 1) LAUNCH_P8S_(AR, BR, 1); else if (ek8 == 2) LAUNCH_P8S_(AR, BR, 2); \
-        else if (ek8 == 3) LAUNCH_P8S_(AR, BR, 3); else if (mih8 != 4) LAUNCH_P8S_(AR, BR, 0); else LAUNCH_P8K_(AR, BR, P8_EK_ANY, 4); } while (0)
-#define LAUNCH_GLDS_(AR, BR) do { if (p8) LAUNCH_P8_(AR, BR); else if (wide) { static bool once = false; if (!once) { once = true; \
-            (void)hipFuncSetAttribute((const void*)gemm_bf16_glds_kernel<AR, BR, 4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 + 128) * 128); } \
-        hipLaunchKernelGGL((gemm_bf16_glds_kernel<AR, BR, 4, 3>), gridw, dim3(512), (size_t)3 * (256 + 128) * 128, st, M, N, K, (const bf16*)A, lda, \
-                           (const bf16*)B, ldb, (bf16*)C, ldc, e, ntn, kchunk, slab); } else { static bool once = false; if (!once) { once = true; \
-            (void)hipFuncSetAttribute((const void*)gemm_bf16_glds_kernel<AR, BR, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); } \
-        hipLaunchKernelGGL((gemm_bf16_glds_kernel<AR, BR, 2, 2>), grid, block, lds, st, M, N, K, (const bf16*)A, lda, \
-                           (const bf16*)B, ldb, (bf16*)C, ldc, e, ntn, kchunk, slab); } } while (0)
-        // wide (256 x 128) tiles when they still give every CU at least ~2 workgroups; A form R needs M % 8 (guaranteed by !safe)
-        const int64_t ntm_w = cdiv(M, 256);
-        const bool wide = dma && !p8 && g_wide_mode != 0 && (g_wide_mode == 2 || ntm_w * ntn * batch * S >= 512);
-        dim3 gridw((unsigned)(ntm_w * ntn), (unsigned)batch, (unsigned)S);
-        // epilogue kind of the 256-row kernel (see p8_tile)
-        const int fmask8 = flags & (EPI_GELU | EPI_GELU_BWD | EPI_RELU_BWD | EPI_ACCUM | EPI_OUT_F32);
-        // (a specialised kind only where every tile is whole: N a multiple of 256 and, unless the launch writes split-K slabs, 16-byte aligned outputs)
-        const bool whole8 = N % 256 == 0 && (S > 1 ? N % 4 == 0 : e.vec != 0);
-        const int ek8 = (g_ablate || !whole8) ? P8_EK_ANY : (S > 1 || fmask8 == 0) ? ((res && S == 1) ? 1 : 0) : (fmask8 == EPI_GELU && !res) ? 2 : (fmask8 == EPI_GELU_BWD && !res) ? 3 : P8_EK_ANY;
-        if (ek8 == P8_EK_ANY && S == 1) mih8 = 4;        // run-time-flag epilogues exist at 256 rows only
-        // a many-round product with a very short K (the local loss' S = C^ Q^^T: 1 872 tiles of 4 K tiles each) is all prologue and epilogue: the
-        // persistent form (224-row tiles only) hides them behind the neighbouring tiles' K loops -- 105 -> 91.5 us -- whatever the planner's height
-        if (plan8 && g_p8_short == 1 && g_p8_persist != 0 && S == 1 && (ek8 == 0 || ek8 == 2) && K / H_BK >= 4 && K / H_BK <= 8 && (K / H_BK) % 2 == 0 &&
-            cdiv(M, 224) * ntn8 > 2 * ncu8) mih8 = 3;
-        const int64_t rows8 = 128 + 32 * mih8;
-        const int64_t ntm8h = cdiv(M, rows8);
-        if (csum_dst && p8 && batch == 1 && S == 1 && e.vec && N % 256 == 0 && !(flags & EPI_OUT_F32)) {
-            e.csum = dvlp_rd_reserve_push(2 * ntm8h, N, csum_dst);     // partial rows: (row tile, upper / lower wave group)
-            csum_fused = e.csum != nullptr;
-        }
-        dim3 grid8((unsigned)(ntm8h * ntn8), (unsigned)batch, (unsigned)S);
-        // persistent form: more than one round of whole tiles, an even number (>= 4) of K tiles, a specialised epilogue, no fused column sums
-        const bool p8p = p8 && g_p8_persist != 0 && mih8 == 3 && M * lda < (1ll << 31) && N * ldb < (1ll << 31) && K * ldb < (1ll << 31) && !transA && S == 1 && batch == 1 && ntm8h * ntn8 > ncu8 && N % 256 == 0 && e.vec && alpha == 1.0f &&
-                         (K / H_BK) % 2 == 0 && K / H_BK >= 4 && (ek8 == 0 || ek8 == 2) && !e.csum;      // (residual / aux-in epilogues: the compiler closes their loads with vmcnt(0) inside the tile loop)
-#define LAUNCH_BF16(AR, BR) do { if (dma) LAUNCH_GLDS_(AR, BR); else if (safe) LAUNCH_BF16_(AR, BR, true); else LAUNCH_BF16_(AR, BR, false); } while (0)
-        rec.kern = p8 ? 2 : dma ? 1 : 0;
-        if (!transA && !transB) LAUNCH_BF16(false, false);
-        else if (!transA && transB) LAUNCH_BF16(false, true);
-        else if (transA && transB) LAUNCH_BF16(true, true);
-        else LAUNCH_BF16(true, false);
-        if (S > 1)
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)cdiv(M * cdiv(N, 8), 256), (unsigned)batch), dim3(256), 0, st, M, N, (int)S,
-                               (const float*)slab, (bf16*)C, ldc, e);
-#undef LAUNCH_BF16_
-#undef LAUNCH_GLDS_
+    // (a split launch of any epilogue kind writes slabs: below 256 rows it runs as kind 0)
+#define LAUNCH_P8_(AR, BR) do { if (pl.ek8 == 0) LAUNCH_P8S_(AR, BR, 0); else if (pl.ek8 == 1) LAUNCH_P8S_(AR, BR, 1); else if (pl.ek8 == 2) LAUNCH_P8S_(AR, BR, 2); \
+        else if (pl.ek8 == 3) LAUNCH_P8S_(AR, BR, 3); else if (pl.mih8 != 4) LAUNCH_P8S_(AR, BR, 0); else LAUNCH_P8K_(AR, BR, P8_EK_ANY, 4); } while (0)
+#define LAUNCH_BF16(AR, BR) do { if (pl.family == GEMM_P8) LAUNCH_P8_(AR, BR); \
+        else if (pl.family == GEMM_WIDE) LAUNCH_((gemm_bf16_glds_kernel<AR, BR, 4, 3>), ntn, kchunk, slab); \
+        else if (pl.family == GEMM_DMA128) LAUNCH_((gemm_bf16_glds_kernel<AR, BR, 2, 2>), ntn, kchunk, slab); \
+        else if (pl.safe) LAUNCH_((gemm_bf16_kernel<AR, BR, true>), ntn, kchunk, slab); \
+        else LAUNCH_((gemm_bf16_kernel<AR, BR, false>), ntn, kchunk, slab); } while (0)
+#define LAUNCH_F32(AR, BR) hipLaunchKernelGGL((gemm_f32_kernel<AR, BR>), grid, block, 0, st, M, N, K, (const float*)A, lda, \
+                                              (const float*)B, ldb, (float*)C, ldc, e, (int)pl.a_vec, (int)pl.b_vec, ntn)
+#define LAUNCH_FORM(L) do { if (!transA && !transB) L(false, false); else if (!transA && transB) L(false, true); \
+        else if (transA && transB) L(true, true); else L(true, false); } while (0)
+    if (pl.family == GEMM_F32) {
+        LAUNCH_FORM(LAUNCH_F32);
+    } else if (pl.family == GEMM_RB) {
+        if (!dvlp_gemm_rb_try(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, batch, strideA, strideB, strideC, st)) return DVLP_ERR_UNSUPPORTED;
+    } else {
+        LAUNCH_FORM(LAUNCH_BF16);
+        if (pl.S > 1)
+            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(pl.reduce_grid, (unsigned)batch), dim3(256), 0, st, M, N, (int)pl.S, (const float*)slab, (bf16*)C, ldc, e);
+    }
+#undef LAUNCH_FORM
+#undef LAUNCH_F32
+#undef LAUNCH_BF16
 #undef LAUNCH_P8_
 #undef LAUNCH_P8S_
-#undef LAUNCH_P8P_
 #undef LAUNCH_P8K_
-#undef LAUNCH_BF16
-    } else {
-        return DVLP_ERR_DTYPE;
-    }
+#undef LAUNCH_
     if (g_prof) { (void)hipEventRecord(rec.b, st); g_recs.push_back(rec); }
+    const bool csum_fused = e.csum != nullptr;
     if (ext) ext->colsum_fused = csum_fused ? 1 : 0;
     if (csum_dst && !csum_fused) {            // not fused: a plain column-sum pass over the stored output (batch 1 only)
         if (int rc = dvlp_launch_status()) return rc;
@@ -1789,6 +1662,23 @@ static int gemm_batched_impl(int dtype, int transA, int transB, int64_t M, int64
     }
     return dvlp_launch_status();
 }
+
+#ifdef DVLP_DEV
+// What dvlp_gemm_batched(...) with / without a column-sum request would launch on `stream` right now (include/demovlp_hip_dev.h).  Host
+// arithmetic only: launches and allocates nothing, dereferences no operand pointer (only their alignment is looked at), runs without a device.
+extern "C" int dvlp_dev_gemm_plan(int dtype, int transA, int transB, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
+                                  const void* B, int64_t ldb, void* C, int64_t ldc, const float* bias, const void* res, int64_t ldres,
+                                  void* aux, int64_t ldaux, int flags, float alpha, int64_t batch, int64_t strideA, int64_t strideB,
+                                  int64_t strideC, int64_t strideRes, int64_t strideAux, int want_colsum, void* stream, int64_t* out) {
+    const GemmProblem pb{dtype, transA, transB, M, N, K, lda, ldb, ldc, ldres, ldaux, batch, strideA, strideB, strideC, strideRes, strideAux, flags, alpha,
+                         bias != nullptr, res != nullptr, aux != nullptr, want_colsum != 0, al16(A), al16(B), al16(C), al16(res), al16(aux), al16(bias)};
+    const GemmPlan pl = plan_for(pb, stream), nq = plan_for(pb, stream, false);
+    const int64_t f[] = {pl.err, pl.family, pl.safe, pl.mih8, pl.S, pl.kchunk, pl.ek8, pl.p8p, pl.csum_fuse, pl.csum_rows, pl.vec, pl.a_vec, pl.b_vec,
+                                                  pl.grid[0], pl.grid[1], pl.grid[2], pl.block, pl.lds, pl.ntm, pl.ntn, pl.reduce_grid, nq.p8p, nq.grid[0]};
+    for (size_t i = 0; i < sizeof f / sizeof *f; ++i) out[i] = f[i];
+    return DVLP_OK;
+}
+#endif
 
 extern "C" int dvlp_gemm_batched(int dtype, int transA, int transB, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
                                  const void* B, int64_t ldb, void* C, int64_t ldc, const float* bias, const void* res, int64_t ldres,
@@ -1852,7 +1742,16 @@ static int wgrad_grouped_impl(int dtype, int count, const int64_t* M, const int6
                               dvlp_wgrad_ext* ext, void* stream) {
     if (count <= 0) return DVLP_OK;
     const int flags = EPI_OUT_F32 | (accumulate ? EPI_ACCUM : 0);
-    bool group_ok = dtype == DVLP_BF16 && g_p8_mode != 0 && g_use_glds && count <= P8G_MAX && count > 1;
+    const GemmKnobs& kn = g_knobs;
+    auto one_by_one = [&]() -> int {                     // the per-problem path: identical results, one dvlp_gemm each
+        for (int p = 0; p < count; ++p) {
+            const int rc = dvlp_gemm(dtype, 1, 1, M[p], N[p], K[p], dY[p], ld_dy[p], X[p], ld_x[p], dW[p], N[p], nullptr, nullptr, 0, nullptr, 0,
+                                     flags, 1.0f, stream);
+            if (rc != DVLP_OK) return rc;
+        }
+        return DVLP_OK;
+    };
+    bool group_ok = dtype == DVLP_BF16 && kn.p8_mode != 0 && kn.use_glds && count <= P8G_MAX && count > 1;
     int64_t T = 0;
     for (int p = 0; group_ok && p < count; ++p) {
         // (K need not be a multiple of the 64-deep K tile: the group covers Km = K - K % 64 rows, the slab reduction adds the rest)
@@ -1864,16 +1763,9 @@ static int wgrad_grouped_impl(int dtype, int count, const int64_t* M, const int6
     bool tails = false;
     for (int p = 0; group_ok && p < count; ++p) { Km[p] = K[p] - K[p] % H_BK; tails = tails || Km[p] != K[p]; }
     // a problem with a K tail needs the slab reduction (at least two K slices): the chip-filling split below gives that when T <= 128
-    if (tails && (T > 128 || g_wgrad_split == 1)) group_ok = false;
+    if (tails && (T > 128 || kn.wgrad_split == 1)) group_ok = false;
     const WsEntry wse = ws_for(stream);
-    if (!group_ok || T > 256 || !wse.ptr) {
-        for (int p = 0; p < count; ++p) {
-            const int rc = dvlp_gemm(dtype, 1, 1, M[p], N[p], K[p], dY[p], ld_dy[p], X[p], ld_x[p], dW[p], N[p], nullptr, nullptr, 0, nullptr, 0,
-                                     flags, 1.0f, stream);
-            if (rc != DVLP_OK) return rc;
-        }
-        return DVLP_OK;
-    }
+    if (!group_ok || T > 256 || !wse.ptr) return one_by_one();
     dvlp_clear_status();
     hipStream_t st = (hipStream_t)stream;
     P8Group g{};
@@ -1888,15 +1780,14 @@ static int wgrad_grouped_impl(int dtype, int count, const int64_t* M, const int6
     // The same K split for every problem of the group (they share K = batch x tokens): measured on MI355X, giving the CUs left over
     // by the uniform split to one problem as a third K slice (108 tiles: S = 3,2,2,2 -> 252 blocks instead of 216) made the whole
     // launch SLOWER -- 403 us against 309 us for a ViT layer's four products, 166 against 122 for a DistilBERT layer's -- although
-    // it shortens a third of the blocks: tools/wgrad_bench.py.  g_wgrad_split > 0 forces a split (A/B measurements).
+    // it shortens a third of the blocks: tools/wgrad_bench.py.  kn.wgrad_split > 0 forces a split (A/B measurements).
     // a co-running group (the text tower's, on its own stream beside the object tower: dvlp_stream_hint) is not split: whole-K blocks on fewer
     // CUs cost less CU-time than twice the blocks plus slabs plus a reduction launch, and the other stream uses what is left
-    // (DVLP_CORUN_WGRAD_SPLIT=1 restores the split for A/B runs)
-    static const bool corun_wsplit = getenv("DVLP_CORUN_WGRAD_SPLIT") && atoi(getenv("DVLP_CORUN_WGRAD_SPLIT")) != 0;
-    if (!tails && !corun_wsplit && g_wgrad_split == 0 && stream_co_running(stream))
+    // (kn.corun_wgrad_split restores the split for A/B runs)
+    if (!tails && !kn.corun_wgrad_split && kn.wgrad_split == 0 && stream_co_running(stream))
         for (int p = 0; p < count; ++p) S[p] = 1;
-    if (g_wgrad_split > 0)
-        for (int p = 0; p < count; ++p) { S[p] = g_wgrad_split; if (S[p] > Km[p] / 256) S[p] = Km[p] / 256 > 0 ? Km[p] / 256 : 1; }
+    if (kn.wgrad_split > 0)
+        for (int p = 0; p < count; ++p) { S[p] = kn.wgrad_split; if (S[p] > Km[p] / 256) S[p] = Km[p] / 256 > 0 ? Km[p] / 256 : 1; }
     // slabs for every split problem must fit the split-K workspace; otherwise split less
     for (;;) {
         int64_t need = 0;
@@ -1912,14 +1803,7 @@ static int wgrad_grouped_impl(int dtype, int count, const int64_t* M, const int6
         for (int p = 0; p < count; ++p) need += S[p] * M[p] * N[p] * 4;
         bool ok = need <= wse.bytes;
         for (int p = 0; p < count; ++p) ok = ok && S[p] >= 2;
-        if (!ok) {                                       // (workspace too small for two slices of everything: the one-product-at-a-time path)
-            for (int p = 0; p < count; ++p) {
-                const int rc = dvlp_gemm(dtype, 1, 1, M[p], N[p], K[p], dY[p], ld_dy[p], X[p], ld_x[p], dW[p], N[p], nullptr, nullptr, 0, nullptr, 0,
-                                         flags, 1.0f, stream);
-                if (rc != DVLP_OK) return rc;
-            }
-            return DVLP_OK;
-        }
+        if (!ok) return one_by_one();                    // (workspace too small for two slices of everything)
     }
     P8GroupReduce r{};
     int blk = 0, rblk = 0, nred = 0;
@@ -1948,7 +1832,7 @@ static int wgrad_grouped_impl(int dtype, int count, const int64_t* M, const int6
     r.count = nred; r.blk0[nred] = rblk;
     // XCD patches (see P8Group): largest first, dealt round-robin, so every XCD gets the same number of blocks where the shapes allow
     g.npatch = 0;
-    if (g_wgrad_patch) {
+    if (kn.wgrad_patch) {
         struct Pt { int p, z, tm, tn, pm, pn; };
         std::vector<Pt> pts;
         bool fits = true;
@@ -1978,8 +1862,8 @@ static int wgrad_grouped_impl(int dtype, int count, const int64_t* M, const int6
     { static bool once = false; if (!once) { once = true;
         (void)hipFuncSetAttribute((const void*)gemm_bf16_p8_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_TOTAL); } }
     g.opt_nblk = 0;
-    if (ext && g_wgrad_ride) {
-        static const int ncu = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
+    if (ext && kn.wgrad_ride) {
+        const int ncu = cu_count();
         int spare = ncu - blk % ncu;                 // CUs the last round of GEMM blocks leaves idle (one workgroup per CU: 136 KB of LDS each)
         if (spare == ncu) spare = 0;
         if (spare > 64) spare = 64;                  // (a co-running, unsplit text-tower group leaves more than the update can use)
@@ -1997,7 +1881,7 @@ static int wgrad_grouped_impl(int dtype, int count, const int64_t* M, const int6
             ext->fused = 1;
         }
     }
-    hipLaunchKernelGGL(gemm_bf16_p8_group_kernel, dim3((unsigned)blk), dim3(512), (size_t)P_LDS_TOTAL, st, g, (accumulate ? EPI_ACCUM : 0) | (g_ablate << 24));
+    hipLaunchKernelGGL(gemm_bf16_p8_group_kernel, dim3((unsigned)blk), dim3(512), (size_t)P_LDS_TOTAL, st, g, (accumulate ? EPI_ACCUM : 0) | (kn.ablate << 24));
     if (nred) hipLaunchKernelGGL(p8_group_reduce_kernel, dim3((unsigned)rblk), dim3(256), 0, st, r, accumulate);
     if (g_prof) { (void)hipEventRecord(rec.b, st); g_recs.push_back(rec); }
     return dvlp_launch_status();

@@ -14,6 +14,7 @@
 // B fragment as the first MFMA operand (the accumulator tile is C^T: a lane holds four consecutive columns of one row), two 16-column
 // blocks are paired with v_permlane16_swap so that a lane owns 8 consecutive columns, as in the 256-row kernel's epilogue (csrc/gemm.hip).
 #include "common.h"
+#include "gemm_plan.h"
 
 typedef unsigned u32x4_rb __attribute__((ext_vector_type(4)));
 
@@ -131,8 +132,7 @@ static void rb_launch(const RbArgs& a, int64_t batch, hipStream_t st) {
 // ordinary dispatch takes it.
 bool dvlp_gemm_rb_try(int transA, int transB, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
                       int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, hipStream_t st) {
-    if (transA || batch < 8 || M < 2048 || N % 8 || K % 8 || N > 288 || K > 288 || lda % 8 || ldb % 8 || ldc % 8 || sA % 8 || sB % 8 || sC % 8) return false;
-    if ((uintptr_t)A % 16 || (uintptr_t)B % 16 || (uintptr_t)C % 16 || M * lda * 2 >= 0x7fffffffll) return false;
+    if (!gemm_rb_fits(transA, transB, M, N, K, lda, ldb, ldc, batch, sA, sB, sC, (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0)) return false;
     static const int ncu = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
     RbArgs a{(const bf16*)A, (const bf16*)B, (bf16*)C, M, N, K, lda, ldb, ldc, sA, sB, sC, 1};
     const int64_t groups = (M + 127) / 128;

@@ -64,7 +64,7 @@ static bool x_general(int64_t G, int64_t W) { return g_force_general || pair_lds
 //   dP2[g,w] = alpha_g S_raw[g,w] - beta_g (P2 Kq)[g,w],   dS_raw[g,w] += alpha_g P2[g,w],   dQ^ -= ((beta P2)^T P2) Q^.
 // Replaces two [.,d]-wide batched products, the wc2 half of the cosine passes and two backward products by one [Bi*G, W] x [W, W]
 // product per caption, two passes over [B,B,G,W] tiles that exist anyway, and W x W products.
-static int g_gram = getenv("DVLP_XATTN_NO_GRAM") ? 0 : 1;
+static int g_gram = 1;
 DVLP_DEV_API int dvlp_dev_xattn_gram(int on) { g_gram = on; return DVLP_OK; }
 static int g_xbwd_packed_fwd();       // (defined below: the Gram form needs the bf16 backward kernel)
 static int g_pairg = 1;          // bf16 backward: dP1 columns in xperm_g order (A/B, tests)
@@ -1337,13 +1337,13 @@ static void launch_pair(bool bwd, int nkg, int nkw, dim3 grid, size_t lds, hipSt
 // The two directions of the loss (image->text / text->image) are independent between the softmax stages, and their contractions and
 // cosine passes are HBM-streaming kernels that reach 2.3-3.2 TB/s alone: the text->image half is issued on an internal side stream
 // beside the image->text half (fork / join by events -- legal inside a hipGraph capture), so the pair fills the memory system.
-// ON by default since round 5 (dvlp_dev_xattn_parallel_halves(0) / DVLP_XATTN_PARALLEL=0 switch it off): -0.2 ms on the B = 64 backward alone
+// ON by default since round 5 (dvlp_dev_xattn_parallel_halves(0) switches it off): -0.2 ms on the B = 64 backward alone
 // (round 3) and -0.13 ms in the replayed step, three alternating runs out of three (18.34 / 18.27 / 18.22 -> 18.18 / 18.11 / 18.15 ms: by
 // then the text tower's stream is idle, so the second half has the chip's spare CUs to itself).  The side stream's split-K products use a
 // slab region of THEIR OWN inside the caller's workspace (XLayout::off_sideslab), registered under the side stream's key for the length
 // of a fork and erased at the join -- a lookup for that stream never reaches the default-stream slabs the main stream's products write.
 // Per call, bit 1 of `gate` (DVLP_XATTN_ONE_STREAM) keeps everything on the caller's stream (bench.py's per-launch timing pass).
-static int g_xpar = (getenv("DVLP_XATTN_PARALLEL") && atoi(getenv("DVLP_XATTN_PARALLEL")) == 0) ? 0 : 1;
+static int g_xpar = 1;
 DVLP_DEV_API int dvlp_dev_xattn_parallel_halves(int on) { g_xpar = on; return DVLP_OK; }
 struct XFork {
     hipStream_t side = nullptr;

@@ -9,8 +9,6 @@ Weight gradients are produced in fp32 straight from the MFMA epilogue.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 
 from . import ops
@@ -152,10 +150,10 @@ def _early_update(params, now=False):
         EARLY_OPT(params, now)
 
 
-FUSE_TEXT_QKV = os.environ.get("DVLP_NO_FUSED_QKV") is None      # developer switch for A/B timing
-FUSE_LN_COLSUM = os.environ.get("DVLP_NO_LN_COLSUM") is None     # developer switch for A/B timing
-FUSE_GEMM_COLSUM = os.environ.get("DVLP_NO_GEMM_COLSUM") is None  # developer switch for A/B timing
-FUSE_ATTN_COLSUM = os.environ.get("DVLP_NO_ATTN_COLSUM") is None  # developer switch for A/B timing
+# developer switches for A/B timing: _lib.call("dvlp_dev_fuse_text_qkv", 0) etc. (developer library only), `bench.py --knob dvlp_dev_fuse_ln_colsum=0`
+FUSE_TEXT_QKV = FUSE_LN_COLSUM = FUSE_GEMM_COLSUM = FUSE_ATTN_COLSUM = True
+for _sw in ("FUSE_TEXT_QKV", "FUSE_LN_COLSUM", "FUSE_GEMM_COLSUM", "FUSE_ATTN_COLSUM"):
+    ops._lib.register_switch(_sw.lower(), __name__, _sw)
 
 
 def _stacked(ts):

@@ -357,10 +357,11 @@ def colsum_grouped(x, M, N, ld, inner, ostride, groups, gstride, out=None):
 # ----------------------------------------------------------------------------------------------------------------
 # LayerNorm
 # ----------------------------------------------------------------------------------------------------------------
-# TIMING-ONLY ablation (DVLP_ABLATE_LN_FWD=1, tools/ln_fusion_bound.sh): the forward LayerNorm launches nothing and hands its INPUT on as its
+# TIMING-ONLY ablation (developer switch dvlp_dev_ln_fwd_ablate: `bench.py --knob dvlp_dev_ln_fwd_ablate=1`, tools/profile_round.sh): the forward LayerNorm launches nothing and hands its INPUT on as its
 # output -- what the step would take if every forward LayerNorm pass were free, i.e. an upper bound on what any fusion of the normalisation
 # into a neighbouring product could buy in the step.  Results are wrong by construction; bench.py marks the line.
-LN_FWD_ABLATE = bool(int(__import__("os").environ.get("DVLP_ABLATE_LN_FWD", "0")))
+LN_FWD_ABLATE = False
+_lib.register_switch("ln_fwd_ablate", __name__, "LN_FWD_ABLATE")
 _LN_ABL = {}
 
 

@@ -4,7 +4,11 @@
  * compile-time constant there, at the default named in its comment (`nm -D libdemovlp_hip.so | grep dvlp_dev_` is empty).  The same
  * sources built with -DDVLP_DEV give demovlp_amd/lib/libdemovlp_hip_dev.so, which exports them on top of everything in
  * demovlp_hip.h; they set process-global state and exist for A/B measurements (tools/), timing ablations and the tests that force a
- * code path (`tests/conftest.py: devlib`).  No module of the package calls one.
+ * code path (`tests/conftest.py: devlib`).  No module of the package calls one.  Neither library reads a switch from the environment.
+ *
+ * Five switches live in Python modules and go through the same door, `demovlp_amd._lib.call("dvlp_dev_<name>", int)`, refused unless this library is
+ * active: ln_fwd_ablate (ops.LN_FWD_ABLATE, TIMING ONLY: results wrong), fuse_text_qkv, fuse_ln_colsum, fuse_gemm_colsum, fuse_attn_colsum
+ * (functional.FUSE_*).
  */
 #ifndef DEMOVLP_HIP_DEV_H
 #define DEMOVLP_HIP_DEV_H
@@ -46,6 +50,23 @@ int dvlp_dev_gemm_resident_b(int on);
 int dvlp_dev_wgrad_group_ride(int on);
 /* number of workgroups a split-K launch aims for (default 768 = 3 per CU) */
 int dvlp_dev_gemm_splitk_target(int64_t n);
+/* a dvlp_gemm launch on a stream marked co-running (dvlp_stream_hint): 0 (default) it is not K-split, 1 it is split like any other --
+   for A/B measurements */
+int dvlp_dev_gemm_corun_split(int on);
+/* a grouped weight-gradient launch on a stream marked co-running: 0 (default) it runs unsplit, 1 it keeps its K split -- for A/B measurements */
+int dvlp_dev_wgrad_corun_split(int on);
+/* What dvlp_gemm_batched with these arguments (want_colsum: a dvlp_gemm_ext::colsum request) would launch on `stream` right now, under the
+   switches above, the split-K workspace and hint registered for the stream and the device's CU count (256 without a device) -- the answer of
+   gemm_plan() (csrc/gemm_plan.h).  Launches and allocates nothing and dereferences no operand pointer (only their 16-byte alignment is looked
+   at), so it runs on a machine without a GPU.  out[0..22]: err (the status dvlp_gemm would return without launching), family (0 fp32, 1 resident-B,
+   2 register-staged, 3 128-row LDS-DMA, 4 wide, 5 256-column), safe, mih8 (tile height 128 + 32 mih8), S, kchunk, ek8 (epilogue kind, 4 = any),
+   p8p (persistent form), csum_fuse, csum_rows, vec, a_vec, b_vec, grid x, y, z, block, dynamic LDS bytes, row tiles, column tiles, grid x of the
+   slab reduction (S > 1), and p8p / grid x again for the case that the deferred-reduction queue has no room for the fused column sums --
+   for tests (tests/test_host_logic.py) */
+int dvlp_dev_gemm_plan(int dtype, int transA, int transB, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                       void* C, int64_t ldc, const float* bias, const void* res, int64_t ldres, void* aux, int64_t ldaux, int flags, float alpha,
+                       int64_t batch, int64_t strideA, int64_t strideB, int64_t strideC, int64_t strideRes, int64_t strideAux, int want_colsum,
+                       void* stream, int64_t* out);
 /* space-mode bf16 backward: 1 (default) one pass over q/k/v/dO with the CLS query folded into the frame tiles, 0 the
    three-launch form -- for A/B measurements and tests. */
 int dvlp_dev_attention_bwd_variant(int merged);

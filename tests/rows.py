@@ -16,8 +16,10 @@ ROWS = {
     "test_product_library_exports_no_developer_switch": "b",
     "test_integration_doc_names_every_entry_point_with_the_reference_interface_it_replaces": "b",
     "test_size_helpers_run_on_host": "b",
+    "test_product_reads_no_developer_variable": "b",
     "test_bad_arguments_are_reported_not_launched": "b",
     "test_no_reference_or_oracle_import_in_product": "b c",
+    "test_gemm_plan_matches_recorded_dispatch": "b A3 A5",
     # ---- tests/test_boundary_init.py
     "test_constructor_initialises_object_tower_like_reference": "b A7",
     "test_factory_builds_from_unchanged_json": "b",

@@ -71,6 +71,43 @@ def test_product_library_exports_no_developer_switch(lib):
     assert not lib.is_dev_library()
 
 
+FORMER_VARIABLES = ["DVLP_ABLATE_LN_FWD", "DVLP_NO_FUSED_QKV", "DVLP_NO_LN_COLSUM", "DVLP_NO_GEMM_COLSUM", "DVLP_NO_ATTN_COLSUM", "DVLP_XATTN_NO_GRAM",
+                    "DVLP_XATTN_PARALLEL", "DVLP_P8_MIN_TILES", "DVLP_P8_ROUNDS", "DVLP_CORUN_SPLIT", "DVLP_CORUN_WGRAD_SPLIT"]
+
+
+def test_product_reads_no_developer_variable(lib):
+    """No stray `DVLP_*` variable changes what the shipped library or package computes or launches: the library holds no such name but
+    DVLP_PROF_REPORT (which only prints), no module of the package reads one from the environment, and with every former variable set a fresh
+    interpreter still has the Python-level switches at their defaults.  They are developer switches now, behind `_lib.call("dvlp_dev_*")`."""
+    import subprocess
+    import sys
+    blob = open(lib.LIB_PATH, "rb").read()
+    assert set(re.findall(rb"DVLP_[A-Z0-9_]+", blob)) <= {b"DVLP_PROF_REPORT"}
+    pkg = os.path.join(ROOT, "demovlp_amd")
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                for ln in open(os.path.join(dirpath, f)):
+                    assert not (re.search(r"environ|getenv", ln) and "DVLP_" in ln), (f, ln)
+    code = ("from demovlp_amd import ops, functional as Fn; "
+            "print(ops.LN_FWD_ABLATE, Fn.FUSE_TEXT_QKV, Fn.FUSE_LN_COLSUM, Fn.FUSE_GEMM_COLSUM, Fn.FUSE_ATTN_COLSUM)")
+    env = {**os.environ, **{v: "1" for v in FORMER_VARIABLES}, "DVLP_XATTN_PARALLEL": "0", "PYTHONPATH": ROOT}
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout
+    assert out.split() == ["False", "True", "True", "True", "True"]
+    lib.use_dev_library(False)
+    from demovlp_amd import ops
+    with pytest.raises(lib.DemoVLPHipError):
+        lib.call("dvlp_dev_ln_fwd_ablate", 1)
+    lib.use_dev_library(True)
+    try:
+        lib.call("dvlp_dev_ln_fwd_ablate", 1)
+        assert ops.LN_FWD_ABLATE is True
+        lib.call("dvlp_dev_ln_fwd_ablate", 0)
+    finally:
+        lib.use_dev_library(False)
+    assert ops.LN_FWD_ABLATE is False
+
+
 def test_size_helpers_run_on_host(lib):
     # pure host arithmetic, safe without a GPU
     assert lib.call("dvlp_layernorm_bwd_blocks", 18496) == 1024

@@ -517,6 +517,55 @@ def test_no_undefined_names_anywhere_in_the_tree():
     assert not bad, "\n".join("%s: %s: undefined name %r" % b for b in bad)
 
 
+def test_gemm_plan_matches_recorded_dispatch():
+    """What dvlp_gemm launches is decided by the pure function gemm_plan (csrc/gemm_plan.h); `dvlp_dev_gemm_plan` (developer library) answers
+    for it without a GPU.  For every row of tests/golden/gemm_plan_cases.json every field of the plan equals what the dispatch code of the commit
+    BEFORE the planner was split out decided for the same call (how the table was recorded: tests/README.md) -- kernel family, safe, tile height,
+    K split, epilogue kind, persistent form, fused column sums, vector flags, grid, block, LDS bytes.  The table itself must reach every family, every
+    tile height and epilogue kind, and agree with two records older than itself: the `kern=` column of profiles/r6_final_gemm_shapes.txt and the
+    block counts the planner's comments state."""
+    import __graft_entry__
+    import gemm_plan_cases as gpc
+    __graft_entry__.build()
+    from demovlp_amd import _lib
+    _lib.use_dev_library(True)
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_plan_cases.json")))
+    listed = gpc.cases()
+    assert [{k: v for k, v in c.items() if k != "expect"} for c in table] == json.loads(json.dumps(listed)), "table and case list out of step"
+    assert len({json.dumps({k: v for k, v in c.items() if k not in ("expect", "name")}, sort_keys=True) for c in table}) == len(table) >= 250
+    for c in table:
+        got = gpc.query(_lib.call, c)
+        assert got == c["expect"], (c["name"], {k: (got[k], c["expect"][k]) for k in got if got[k] != c["expect"][k]})
+    # coverage of the recorded table
+    ok = [c["expect"] for c in table if c["expect"]["err"] == 0]
+    fam = gpc.FAMILIES
+    assert {e["family"] for e in ok} == set(fam.values())
+    assert {e["safe"] for e in ok if e["family"] == fam["reg"]} == {0, 1}
+    p8 = [e for e in ok if e["family"] == fam["p8"]]
+    assert {e["mih8"] for e in p8} == {1, 2, 3, 4} and {e["ek8"] for e in p8} == {0, 1, 2, 3, 4}
+    assert any(e["p8p"] for e in p8) and any(not e["p8p"] for e in p8) and any(e["S"] > 1 for e in p8) and any(e["S"] > 1 for e in ok if e["family"] == fam["g128"])
+    assert any(e["csum_fuse"] and e["p8p_noqueue"] and not e["p8p"] for e in p8)          # the persistent form gives way to fused column sums only
+    assert {c["expect"]["err"] for c in table} == {0, -1, -2}
+    assert {n for c in table for n in c["knobs"]} == set(gpc.KNOB_DEFAULTS)
+    changed = {n for c in table for n in c["knobs"] if gpc.query(_lib.call, dict(c, knobs={})) != c["expect"]}
+    assert changed == set(gpc.KNOB_DEFAULTS)                                              # every switch changes the plan of at least one of its cases
+    # evidence older than the table: kernel family per profiled shape (the profile's `reg` is its label for everything that is neither `g128` nor `p8`:
+    # there, the resident-B kernel) ...
+    prof = [c for c in table if "kern" in c and c["ws"] and c["corun"] == 0]
+    assert len(prof) == len(gpc.profile_rows()) == 34
+    for c in prof:
+        want = {"g128": fam["g128"], "p8": fam["p8"], "reg": fam["rb"]}[c["kern"]]
+        assert c["expect"]["family"] == want, c["name"]
+    # ... and the block counts of the planner's comments: M = 18496 as 83 row tiles x {3, 9, 12} column tiles, M = 6400 as 120 / 480 blocks of 160 rows,
+    # its K = 3072 products as two slices
+    e = {(c["form"], c["M"], c["N"], c["K"]): c["expect"] for c in prof}
+    for N, K, nt in ((768, 768, 3), (2304, 768, 9), (3072, 768, 12)):
+        x = e["KK", 18496, N, K]
+        assert (x["mih8"], x["ntm"], x["ntn"], x["S"]) == (3, 83, nt, 1) and x["grid_x"] == (256 if x["p8p"] else 83 * nt)
+    assert [(e["KK", 6400, N, 768][k]) for N in (768, 3072) for k in ("mih8", "grid_x", "S")] == [1, 120, 1, 1, 480, 1]
+    assert [(e[f, 6400, 768, 3072][k]) for f in ("KK", "KR") for k in ("mih8", "grid_x", "grid_z", "S")] == [1, 120, 2, 2, 1, 120, 2, 2]
+
+
 def test_every_test_is_mapped_to_a_survey_row():
     """tests/rows.py is the row-by-row index of the suite: every test function must name the row(s) it covers, every row
     must be covered by at least one GPU test where it is a device path, and the map must not name functions that no longer exist."""

@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B of bench.py under different ENVIRONMENT settings in one GPU session: tools/ab_env.sh OUTDIR "ENV1=.. ENV2=.." "..." (each variant twice, interleaved;
-# a variant may also carry bench flags after a '|': "DVLP_P8_MIN_TILES=64|--overlap-wgrad 2")
+# a variant may also carry bench flags after a '|': "DVLP_OVERLAP_TEXT_ONLY=1|--overlap-wgrad 2 --knob dvlp_dev_gemm_corun_split=1"; the product reads
+# no variable of its own: developer switches go through --knob)
 out=$1; shift
 mkdir -p "$out"
 for rep in 1 2; do

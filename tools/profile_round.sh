@@ -34,7 +34,7 @@ timeout 600 python3 $R/bench.py --full --frames 32 --batch 16 --steps 6 --warmup
 # config 4 (configs/ft/msrvtt_o2t-select.json geometry: F = 8, R = 30, per-GPU batch 32 -> 7712 tokens): its own throughput line
 timeout 600 python3 $R/bench.py --full --batch 32 --regions 30 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_f8_r30_b32.json 2> $O/bench_c4.err
 # TIMING-ONLY: what the step would take if every forward LayerNorm pass were free (an upper bound for fusing LayerNorm into a neighbouring product)
-DVLP_ABLATE_LN_FWD=1 timeout 600 python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-kernel-timing > $O/ln_fusion_bound.json 2> $O/ln_bound.err
+timeout 600 python3 $R/bench.py --knob dvlp_dev_ln_fwd_ablate=1 --full --steps 20 --warmup 3 --no-cpu-baseline --no-kernel-timing > $O/ln_fusion_bound.json 2> $O/ln_bound.err
 # (tile height, K split) sweep of the 256-column kernel on the text tower's, config 4's and the object tower's shapes; the local loss' contractions
 (timeout 400 python3 $R/tools/tile_sweep.py text; timeout 300 python3 $R/tools/tile_sweep.py c4; timeout 400 python3 $R/tools/tile_sweep.py obj) > $O/tile_sweep.txt 2>&1
 timeout 300 python3 $R/tools/loss_gemm_bench.py > $O/loss_gemm_bench.txt 2>&1
