@@ -1590,6 +1590,37 @@ extern "C" int dvlp_xattn_index_pairs_fwd(int64_t capacity, int64_t G, const voi
     return dvlp_launch_status();
 }
 
+// grounding of the pairs of dvlp_xattn_index_pairs_fwd: the same score (bit for bit) plus where it came from.  Anything wrong with the
+// arguments, a shape beyond the fused range included, is DVLP_ERR_SHAPE; nothing is launched then.
+int dvlp_xfused_index_pairs_ground(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, const void* Qraw,
+                                   const float* mcap, int64_t K, const int* cand, int frames, float lam, int gate, float* scores, float* word_scores,
+                                   float* region_scores, int* word_region, float* word_weight, int* region_word, float* frame_scores,
+                                   void* workspace, hipStream_t st);
+
+extern "C" int64_t dvlp_xattn_index_ground_workspace_bytes(int64_t Bj, int64_t W, int64_t K, int64_t G) {
+    if (Bj <= 0 || W <= 0 || K <= 0 || G <= 0 || Bj > 65535 || Bj * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    return dvlp_xfused_query_bytes(Bj, W);                          // the caption-side prep; the cross-wave exchange lives in dead LDS
+}
+
+extern "C" int dvlp_xattn_index_pairs_ground(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                             const void* Qraw, const float* mcap, const int* cand, int64_t K, int64_t frames, float lam, int gate,
+                                             float* score, float* word_scores, float* region_scores, int* word_region, float* word_region_weight,
+                                             int* region_word, float* frame_scores, void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != XD || capacity <= 0 || capacity > INT32_MAX || G <= 0 || Bj <= 0 || W <= 0 || K < 1) return DVLP_ERR_SHAPE;
+    if (Bj > 65535 || Bj * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mimg || !Qraw || !mcap || !cand || !score || !word_scores || !region_scores || !word_region || !word_region_weight ||
+        !region_word || !workspace)
+        return DVLP_ERR_SHAPE;
+    // frames = 0 <=> no frame_scores; otherwise frames must divide G
+    if (frames < 0 || frames > G || (frames == 0) != (frame_scores == nullptr) || (frames > 0 && G % frames != 0)) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, W)) return DVLP_ERR_SHAPE;
+    dvlp_xfused_index_pairs_ground(capacity, G, index, mimg, Bj, W, Qraw, mcap, K, cand, (int)frames, lam, gate & 1, score, word_scores,
+                                   region_scores, word_region, word_region_weight, region_word, frame_scores, workspace, (hipStream_t)stream);
+    return dvlp_launch_status();
+}
+
 // workspace must be the one dvlp_xattn_fwd(..., bwd=1) filled.  Outputs: dC [Bi][G][d], dQ [Bj][W][d] (compute dtype).
 extern "C" int dvlp_xattn_bwd(int dtype, int64_t Bi, int64_t Bj, int64_t G, int64_t W, int64_t d, const void* Craw, const void* Qraw,
                               const float* mimg, const float* mcap, float lam, int gate, const float* dscores, void* workspace,

@@ -201,7 +201,13 @@ __device__ __forceinline__ void pair_forward(const FusedArgs& a, char* smem, int
         for (int r = 0; r < 4; ++r) {
             float q = 0.f;
 #pragma unroll
-            for (int nb = 0; nb < FW_MAXB; ++nb) { const float v = R.S[s][nb][r]; q += v * v; csq[nb] += v * v; }
+            // (q += v * v; csq[nb] += v * v, with the contraction written out -- a product at the head of each sum, fused multiply-adds after it --
+            //  so that every instantiation of this code rounds alike: left to the optimiser, the grounding kernel got packed products and separate adds)
+            for (int nb = 0; nb < FW_MAXB; ++nb) {
+                const float v = R.S[s][nb][r];
+                q = nb == 0 ? v * v : fmaf(v, v, q);
+                csq[nb] = (s == 0 && r == 0) ? v * v : fmaf(v, v, csq[nb]);
+            }
             R.rn[s][r] = 1.f / (sqrtf(row16_sum(q)) + 1e-8f);
             k1[s][r] = L2E * R.rn[s][r];
             mi[s][r] = L2E * (mi[s][r] - 1.f);            // exponent offset: lam log2(e) (m_img - 1); z <= lam, so no max pass is needed
@@ -345,9 +351,105 @@ __device__ __forceinline__ void pair_forward(const FusedArgs& a, char* smem, int
     }
 }
 
-// The score of one (video i, caption j) pair -> *out: the whole forward of both launch shapes below (full grid, pair list), so that a
-// pair's arithmetic -- and its result, bit for bit -- does not depend on which of them computed it.
-__device__ __forceinline__ void xf_pair_score(const FusedArgs& a, char* smem, int i, int j, float* out) {
+// ---- grounding (xf_index_pairs_ground_kernel): where one pair's score came from.  Rows of ONE pair; see DESIGN.md 6e.
+struct GroundOut {
+    float *word_scores, *region_scores;        // [W], [G]: the cosines whose means are the score
+    int *word_region, *region_word;            // [W], [G]: argmax of the image->text logit over regions / of the text->image logit over words
+    float *word_weight;                        // [W]: P1'[w][word_region[w]]
+    float* frame_scores;                       // [frames] or NULL
+    int frames;
+};
+// "larger logit, then smaller index" as ONE unsigned comparison (the order of csrc/topk.hip): the float mapped to an unsigned that sorts like
+// it in the high word, ~index in the low word.  0 is below every key of a real entry and stands for "no entry" (padding).
+typedef unsigned long long u64;
+__device__ __forceinline__ u64 gr_key(float v, int index) {
+    const unsigned u = __float_as_uint(v);
+    return ((u64)(u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u)) << 32) | (u64)(0xffffffffu - (unsigned)index);
+}
+// lam (s n + m).  Written as instructions, not as C++ arithmetic: the optimiser packs and contracts floating-point expressions by what else
+// the function holds (see the squared norms in pair_forward), and the score must not depend on that.  Through here the grounding adds no
+// floating-point expression for it to weigh against the shared per-pair code.
+__device__ __forceinline__ float gr_logit(float lam, float s, float n, float m) {
+    float x;
+    asm("v_fma_f32 %0, %1, %2, %3\n\tv_mul_f32 %0, %0, %4" : "=&v"(x) : "v"(s), "v"(n), "v"(m), "v"(lam));
+    return x;
+}
+__device__ __forceinline__ int gr_index(u64 k) { return (int)(0xffffffffu - (unsigned)k); }
+__device__ __forceinline__ u64 gr_max(u64 a, u64 b) { return a > b ? a : b; }
+template <int CTRL>
+__device__ __forceinline__ u64 gr_dpp_max(u64 x) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)x, CTRL, 0xf, 0xf, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(x >> 32), CTRL, 0xf, 0xf, true);
+    return gr_max(x, ((u64)hi << 32) | lo);
+}
+// all-reduce inside each 16-lane row / over the four lanes that share lane & 15 (row16_sum / col4_sum of common.h, for keys)
+__device__ __forceinline__ u64 gr_row16_max(u64 k) {
+    k = gr_dpp_max<0xB1>(k); k = gr_dpp_max<0x4E>(k); k = gr_dpp_max<0x141>(k); k = gr_dpp_max<0x140>(k);
+    return k;
+}
+__device__ __forceinline__ u64 gr_col4_max(u64 k) {
+    {
+        auto lo = __builtin_amdgcn_permlane16_swap((unsigned)k, (unsigned)k, false, false);
+        auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(k >> 32), (unsigned)(k >> 32), false, false);
+        k = gr_max(((u64)hi[0] << 32) | lo[0], ((u64)hi[1] << 32) | lo[1]);
+    }
+    auto lo = __builtin_amdgcn_permlane32_swap((unsigned)k, (unsigned)k, false, false);
+    auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(k >> 32), (unsigned)(k >> 32), false, false);
+    return gr_max(((u64)hi[0] << 32) | lo[0], ((u64)hi[1] << 32) | lo[1]);
+}
+
+// Both argmaxes of one pair from the fp32 accumulators pair_forward leaves in R (not from the bf16 P1' / P2' tiles, whose rounding makes
+// ties the reference does not have).  region_word[g]: row g lives in one 16-lane row of one wave -> written here.  word_region[w]: column w
+// is spread over the eight waves -> this wave's best key per word goes to keys [8][112] (u64) over the exchange rows xa, xb, both dead once a
+// wave is past the last barrier of pair_forward (xa and xb are last read before that barrier, by every wave); xf_pair_score finishes them.
+__device__ __forceinline__ void ground_argmax(const FusedArgs& a, char* smem, int i, int j, const PairRegs& R, const GroundOut& go) {
+    const int tid = threadIdx.x, lane = tid & 63, lq = lane >> 4, lc = lane & 15;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nbg = a.Gr >> 4, nwb = a.Wp >> 4;
+    const float* mimg = a.mimg + (int64_t)i * a.G;
+    const float* mcap = a.mcap + (int64_t)j * a.W;
+    u64* keys = (u64*)(smem + flds(a.Gr, a.Gk, a.Wp, a.Wk).xa);
+    float mc[FW_MAXB];
+    bool okw[FW_MAXB];
+    u64 kw[FW_MAXB];
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) {
+        const int w = nb * 16 + lc;
+        okw[nb] = nb < nwb && w < a.W;
+        mc[nb] = okw[nb] ? mcap[w] : 0.f;
+        kw[nb] = 0ull;
+    }
+#pragma unroll
+    for (int s = 0; s < FG_SLOTS; ++s) {
+        const int rb = wid + 8 * s;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int g = rb * 16 + lq * 4 + r;
+            const bool okg = rb < nbg && g < a.G;
+            const float mi = okg ? mimg[g] : 0.f;
+            u64 kg = 0ull;
+#pragma unroll
+            for (int nb = 0; nb < FW_MAXB; ++nb) {
+                const float sv = R.S[s][nb][r];
+                if (okg) kw[nb] = gr_max(kw[nb], gr_key(gr_logit(a.lam, sv, R.rn[s][r], mi), g));                // lam (A[g][w] + m_img[g])
+                if (okw[nb]) kg = gr_max(kg, gr_key(gr_logit(a.lam, sv, R.cn[nb], mc[nb]), nb * 16 + lc));       // lam (A2[g][w] + m_cap[w])
+            }
+            kg = gr_row16_max(kg);
+            if (okg && lc == 0) go.region_word[g] = gr_index(kg);
+        }
+    }
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) {
+        const u64 k = gr_col4_max(kw[nb]);
+        if (lq == 0 && nb < nwb) keys[wid * 112 + nb * 16 + lc] = k;
+    }
+}
+
+// The score of one (video i, caption j) pair -> *out: the whole forward of every launch shape below (full grid, pair lists), so that a
+// pair's arithmetic -- and its result, bit for bit -- does not depend on which of them computed it.  GROUND adds the rows of `go` and one
+// barrier; it changes no operand and no order of the arithmetic that ends in *out.
+template <bool GROUND>
+__device__ __forceinline__ void xf_pair_score(const FusedArgs& a, char* smem, int i, int j, float* out, const GroundOut& go) {
     const int tid = threadIdx.x, lane = tid & 63, lq = lane >> 4, lc = lane & 15;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nbg = a.Gr >> 4, nwb = a.Wp >> 4;
@@ -363,6 +465,7 @@ __device__ __forceinline__ void xf_pair_score(const FusedArgs& a, char* smem, in
     {
         PairRegs R;
         pair_forward(a, smem, i, j, R);
+        if constexpr (GROUND) ground_argmax(a, smem, i, j, R, go);
     }
     // A operands of the two context products (this wave's 32 channels of C^^T and Q^^T) are requested BEFORE the barrier that
     // publishes P1' / P2': their L2 latency runs under the wait for the slowest wave
@@ -385,6 +488,19 @@ __device__ __forceinline__ void xf_pair_score(const FusedArgs& a, char* smem, in
     }
     __syncthreads();
     if (a.stop >= 1 && a.stop <= 4) { if (tid == 0) *out = dotg[0] + dotw[0]; return; }
+    if constexpr (GROUND) {
+        // word w: the best of the eight waves' keys, and its weight from the published P1' tile (P1' is overwritten after the next product)
+        if (tid < a.W) {
+            const u64* keys = (const u64*)(smem + L.xa);
+            u64 k = 0ull;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) k = gr_max(k, keys[w * 112 + tid]);
+            const int g = gr_index(k);
+            go.word_region[tid] = g;
+            go.word_weight[tid] = (float)P1s[tid * p1s + g];
+        }
+        __syncthreads();                                   // the keys are read: xa takes the |wc|^2 partials below
+    }
 
     // ---- |wc_w|^2: wc^T [d][w] = C^^T [d][g] P1'^T; wave wid owns channels 32 wid .. 32 wid + 31
     {
@@ -461,11 +577,15 @@ __device__ __forceinline__ void xf_pair_score(const FusedArgs& a, char* smem, in
     const float* nc = a.nc + (int64_t)i * a.G;
     for (int w = tid; w < a.W; w += blockDim.x) {
         const float n = nq[w];
-        part += dotw[w] * (n + 1e-8f) / fmaxf(n * sqrtf(nw1[w]), 1e-8f) / (float)a.W;
+        const float c = dotw[w] * (n + 1e-8f) / fmaxf(n * sqrtf(nw1[w]), 1e-8f);
+        if constexpr (GROUND) go.word_scores[w] = c;
+        part += c / (float)a.W;
     }
     for (int g = tid; g < a.G; g += blockDim.x) {
         const float n = nc[g];
-        part += dotg[g] * (n + 1e-8f) / fmaxf(n * sqrtf(nw2[g]), 1e-8f) / (float)a.G;
+        const float c = dotg[g] * (n + 1e-8f) / fmaxf(n * sqrtf(nw2[g]), 1e-8f);
+        if constexpr (GROUND) { go.region_scores[g] = c; nw2[g] = c; }      // (nw2[g] is this thread's own entry: kept for the frame means)
+        part += c / (float)a.G;
     }
     part = wave_sum(part);
     float* red = (float*)(smem + L.xb);
@@ -476,13 +596,25 @@ __device__ __forceinline__ void xf_pair_score(const FusedArgs& a, char* smem, in
         for (int w = 0; w < 8; ++w) t += red[w];
         *out = t;
     }
+    if constexpr (GROUND) {
+        // frame f: mean of the region cosines (nw2, published by the barrier above) over its unmasked regions, summed in region order
+        if (go.frame_scores && tid < go.frames) {
+            const float* mimg = a.mimg + (int64_t)i * a.G;
+            const int rf = a.G / go.frames;
+            float t = 0.f;
+            int n = 0;
+            for (int g = tid * rf; g < (tid + 1) * rf; ++g)
+                if (mimg[g] == 0.f) { t += nw2[g]; ++n; }
+            go.frame_scores[tid] = n ? t / (float)n : -__builtin_inff();
+        }
+    }
 }
 
 // full grid: workgroup (j, i) -> scores[i][j]
 __global__ __launch_bounds__(512) void xf_fwd_kernel(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int j = blockIdx.x, i = blockIdx.y;
-    xf_pair_score(a, smem, i, j, a.scores + (int64_t)i * a.Bj + j);
+    xf_pair_score<false>(a, smem, i, j, a.scores + (int64_t)i * a.Bj + j, GroundOut{});
 }
 
 // pair list: workgroup (k, i) -> scores[i][k], caption cand[i K + k]; an index outside [0, Bj) reads nothing and scores NaN
@@ -495,7 +627,7 @@ __global__ __launch_bounds__(512) void xf_pairs_fwd_kernel(FusedArgs a) {
         if (threadIdx.x == 0) a.scores[o] = __builtin_nanf("");
         return;
     }
-    xf_pair_score(a, smem, i, j, a.scores + o);
+    xf_pair_score<false>(a, smem, i, j, a.scores + o, GroundOut{});
 }
 
 // resident index, query-major pair list: workgroup (k, j) -> scores[j][k], video cand[j K + k] of the index (a.Bi = its capacity); an index
@@ -509,7 +641,29 @@ __global__ __launch_bounds__(512) void xf_index_pairs_kernel(FusedArgs a) {
         if (threadIdx.x == 0) a.scores[o] = __builtin_nanf("");
         return;
     }
-    xf_pair_score(a, smem, i, j, a.scores + o);
+    xf_pair_score<false>(a, smem, i, j, a.scores + o, GroundOut{});
+}
+
+// the same grid with grounding: `go` holds the bases of the [Bj][K][...] output arrays; pair o = j K + k writes row o of each.  An index
+// outside [0, capacity) reads nothing: NaN in the float rows, -1 in the int rows.
+__global__ __launch_bounds__(512) void xf_index_pairs_ground_kernel(FusedArgs a, GroundOut go) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int j = blockIdx.y;
+    const int64_t o = (int64_t)j * a.K + blockIdx.x;
+    const int i = a.cand[o];
+    go.word_scores += o * a.W; go.word_region += o * a.W; go.word_weight += o * a.W;
+    go.region_scores += o * a.G; go.region_word += o * a.G;
+    if (go.frame_scores) go.frame_scores += o * go.frames;
+    if (i < 0 || i >= a.Bi) {
+        const float nan = __builtin_nanf("");
+        if (threadIdx.x == 0) a.scores[o] = nan;
+        for (int t = threadIdx.x; t < a.W; t += blockDim.x) { go.word_scores[t] = nan; go.word_weight[t] = nan; go.word_region[t] = -1; }
+        for (int t = threadIdx.x; t < a.G; t += blockDim.x) { go.region_scores[t] = nan; go.region_word[t] = -1; }
+        if (go.frame_scores)
+            for (int t = threadIdx.x; t < go.frames; t += blockDim.x) go.frame_scores[t] = nan;
+        return;
+    }
+    xf_pair_score<true>(a, smem, i, j, a.scores + o, go);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -620,8 +774,9 @@ int dvlp_xfused_index_add(int64_t capacity, int64_t G, int64_t row0, int64_t n, 
     return 0;
 }
 
-int dvlp_xfused_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, const void* Qraw,
-                                const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores, void* workspace, hipStream_t st) {
+// prep of the Bj captions into the workspace; the kernel arguments of the index pair kernels
+static FusedArgs xf_index_prep(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, const void* Qraw,
+                               const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores, void* workspace, hipStream_t st) {
     const IndexLayout I = index_layout(capacity, G);
     const QueryLayout Q = query_layout(Bj, W);
     const char* ix = (const char*)index;
@@ -635,9 +790,32 @@ int dvlp_xfused_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, 
     const int64_t rq = Q.Wp > Q.Wk ? Q.Wp : Q.Wk;
     hipLaunchKernelGGL(xf_prep_kernel, dim3((unsigned)cdiv(Bj * rq, 4)), dim3(256), 0, st, (int)Bj, (int)W, (int)Q.Wp, (int)Q.Wk, (const bf16*)Qraw,
                        (bf16*)(ws + Q.off_qhat), (bf16*)(ws + Q.off_qhatT), (float*)(ws + Q.off_nq));
+    return a;
+}
+
+int dvlp_xfused_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, const void* Qraw,
+                                const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores, void* workspace, hipStream_t st) {
+    const FusedArgs a = xf_index_prep(capacity, G, index, mimg, Bj, W, Qraw, mcap, K, cand, lam, gate, scores, workspace, st);
     const FLds L = flds(a.Gr, a.Gk, a.Wp, a.Wk);
     { static bool once = false; if (!once) { once = true;
         (void)hipFuncSetAttribute((const void*)xf_index_pairs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
     hipLaunchKernelGGL(xf_index_pairs_kernel, dim3((unsigned)K, (unsigned)Bj), dim3(512), (size_t)L.total, st, a);
+    return 0;
+}
+
+// grounding of the same pairs (dvlp_xattn_index_pairs_ground): the same prep and grid; no ablation switch reaches it
+int dvlp_xfused_index_pairs_ground(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, const void* Qraw,
+                                   const float* mcap, int64_t K, const int* cand, int frames, float lam, int gate, float* scores, float* word_scores,
+                                   float* region_scores, int* word_region, float* word_weight, int* region_word, float* frame_scores,
+                                   void* workspace, hipStream_t st) {
+    FusedArgs a = xf_index_prep(capacity, G, index, mimg, Bj, W, Qraw, mcap, K, cand, lam, gate, scores, workspace, st);
+    a.stop = 0;
+    GroundOut go{};
+    go.word_scores = word_scores; go.region_scores = region_scores; go.word_region = word_region; go.region_word = region_word;
+    go.word_weight = word_weight; go.frame_scores = frame_scores; go.frames = frames;
+    const FLds L = flds(a.Gr, a.Gk, a.Wp, a.Wk);
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xf_index_pairs_ground_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xf_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bj), dim3(512), (size_t)L.total, st, a, go);
     return 0;
 }

@@ -817,6 +817,36 @@ def xattn_index_pairs_fwd(index, capacity, G, m_img, Q, m_cap, cand, lam, gate):
     return scores
 
 
+def xattn_index_pairs_ground(index, capacity, G, m_img, Q, m_cap, cand, lam, gate, frames=None):
+    """The pairs of ``xattn_index_pairs_fwd`` with their grounding (``dvlp_xattn_index_pairs_ground``, same arguments): a dict of
+    ``score`` fp32 [Bj, K] (bit-equal to ``xattn_index_pairs_fwd``), ``word_scores`` fp32 [Bj, K, W], ``region_scores`` fp32 [Bj, K, G],
+    ``word_region`` int32 [Bj, K, W], ``word_region_weight`` fp32 [Bj, K, W], ``region_word`` int32 [Bj, K, G] and, with ``frames`` (a divisor
+    of G), ``frame_scores`` fp32 [Bj, K, frames].  An entry of cand outside [0, capacity) gives NaN / -1 rows.  Forward only."""
+    if Q.dtype != torch.bfloat16:
+        raise _lib.DemoVLPHipError(f"the resident video index is bf16 only, got {Q.dtype}")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != Q.shape[0]:
+        raise _lib.DemoVLPHipError(f"cand must be int32 [Bj, K], got {cand.dtype} {tuple(cand.shape)}")
+    if tuple(m_img.shape) != (capacity, G) or tuple(m_cap.shape) != tuple(Q.shape[:2]):
+        raise _lib.DemoVLPHipError(f"masks must be [capacity, G] and [Bj, W], got {tuple(m_img.shape)} and {tuple(m_cap.shape)}")
+    if frames is not None and (int(frames) < 1 or G % int(frames) != 0):
+        raise _lib.DemoVLPHipError(f"frames = {frames} must be a positive divisor of G = {G}")
+    require_gpu(index, m_img, Q, m_cap, cand)
+    Bj, W, d = Q.shape
+    K = cand.shape[1]
+    F = 0 if frames is None else int(frames)
+    ws = torch.empty(_size("dvlp_xattn_index_ground_workspace_bytes", Bj, W, K, int(G)), device=Q.device, dtype=torch.uint8)
+    new = lambda n, dtype: torch.empty((Bj, K, n), device=Q.device, dtype=dtype)
+    out = dict(score=torch.empty((Bj, K), device=Q.device, dtype=torch.float32), word_scores=new(W, torch.float32),
+               region_scores=new(G, torch.float32), word_region=new(W, torch.int32), word_region_weight=new(W, torch.float32),
+               region_word=new(G, torch.int32))
+    if F:
+        out["frame_scores"] = new(F, torch.float32)
+    call("dvlp_xattn_index_pairs_ground", int(capacity), int(G), p(index), p(m_img), Bj, W, d, p(Q), p(m_cap), p(cand), K, F, float(lam),
+         _gate_bits(gate) & 1, p(out["score"]), p(out["word_scores"]), p(out["region_scores"]), p(out["word_region"]),
+         p(out["word_region_weight"]), p(out["region_word"]), p(out["frame_scores"]) if F else None, p(ws), stream())
+    return out
+
+
 def topk_rows(x, K, N=None, index_base=0, out=None, merge=False):
     """x fp32 [M, ld] (first N columns; default all) -> (val fp32 [M, K], idx int32 [M, K]): per row the K largest values in descending order,
     ties by smaller index (np.argsort(-x, kind="stable")[:, :K] + index_base), NaN last, (-inf, -1) where N < K.  ``out`` = (val, idx) to write

@@ -10,6 +10,11 @@ touches the object tower or re-prepares a video.  ``VideoIndex.search`` is two s
   local    the (region x word) similarity of each query against its shortlisted videos only (``dvlp_xattn_index_pairs_fwd``: the per-pair
            code of the full-grid kernel, bit-equal to its entries), added to the cosine, and a last ``dvlp_topk_rows`` for the ``k`` best.
 
+``VideoIndex.ground`` / ``search(..., ground=True)`` say where a result matched: for the k winners one more launch
+(``dvlp_xattn_index_pairs_ground``, the pair kernel's own arithmetic) returns the per-word and per-region cosines the local score is the
+mean of, each word's strongest region (and frame) with its attention weight, each region's strongest word and per-frame means.  Fused route
+only.
+
 Orientation.  The score of (caption j, video i) is ``cos(text_j, video_i) + local(video_i, caption_j)``.  ``trainer.evaluate`` reproduces
 the reference's quirk of adding the global [text, video] and local [video, text] matrices element-wise without a transpose
 (trainer/trainer_dist.py:369-399); search does not.  In ``evaluate``'s terms the search score is ``global_sims + local_sims.T``, and metrics
@@ -161,9 +166,8 @@ class VideoIndex:
             out[j] = local_loss.get_sim(self.local[rows], lt[j:j + 1], self.om[rows], None, text_mask[j:j + 1])[:, 0]
         return out
 
-    def _score(self, model, loss_fn, text, S, chunk):
-        """One block of queries through the text tower and both stages -> (qn, ids int32 [Nq, S], cos, local)."""
-        local_loss = getattr(loss_fn, "local_loss", loss_fn)
+    def _text_side(self, model, text):
+        """One block of queries through the text tower -> (global [Nq, 256], local [Nq, W, 256], additive word mask [Nq, W])."""
         att = text["attention_mask"]
         text_mask = (att[:, 1:].contiguous() - 1.0) * 100.0        # as trainer.evaluate (trainer/trainer_dist.py:156-159)
         gt, lt = model.compute_text(text)
@@ -171,13 +175,66 @@ class VideoIndex:
             raise ValueError(f"this index holds {self.dtype} embeddings, the model computes {lt.dtype}")
         if self.fused and call("dvlp_xattn_index_query_workspace_bytes", lt.shape[0], lt.shape[1]) < 0:
             raise DemoVLPHipError(f"captions of {lt.shape[1]} words are beyond the fused kernel's range (W <= 112)")
+        return gt, lt.contiguous(), text_mask
+
+    def _score(self, model, loss_fn, text, S, chunk, side=None):
+        """One block of queries through the text tower (or its outputs ``side``) and both stages -> (qn, ids int32 [Nq, S], cos, local)."""
+        local_loss = getattr(loss_fn, "local_loss", loss_fn)
+        gt, lt, text_mask = side if side is not None else self._text_side(model, text)
         qn = ops.rownorm_fwd(gt.contiguous())[0]
         ids, cos = self._global_stage(qn, S, chunk)
-        return qn, ids, cos, self._local_stage(local_loss, lt.contiguous(), text_mask, ids)
+        return qn, ids, cos, self._local_stage(local_loss, lt, text_mask, ids)
 
-    def search(self, model, loss_fn, text, k=10, shortlist=100, chunk=65536):
+    def _ground_block(self, loss_fn, side, att, ids, frames):
+        """Grounding of one block's pairs (query j, index row ids[j, p]) from its text-tower outputs."""
+        local_loss = getattr(loss_fn, "local_loss", loss_fn)
+        _, lt, text_mask = side
+        out = ops.xattn_index_pairs_ground(self.local, self.capacity, self.G, self.om, lt, text_mask, ids.to(torch.int32).contiguous(),
+                                           float(local_loss.lambda_softmax), local_loss.focal_type == "equal", frames)
+        out["word_valid"] = att[:, 1:] > 0
+        if frames is not None:
+            out["word_frame"] = torch.div(out["word_region"], self.G // int(frames), rounding_mode="floor")
+        return out
+
+    def _ground_checks(self, frames):
+        if not self.fused:
+            raise DemoVLPHipError("grounding needs the fused route (a bf16 index with G <= 288, captions of W <= 112 words): this index is "
+                                  f"{self.dtype} with G = {self.G}; there is no fp32 / long-video grounding")
+        if frames is not None and (int(frames) < 1 or self.G % int(frames) != 0):
+            raise ValueError(f"frames = {frames} must be a positive divisor of G = {self.G}")
+
+    def ground(self, model, loss_fn, text, ids, frames=None):
+        """Where the local similarity of (query j, index row ``ids[j, p]``) comes from; ``ids`` int [Nq, k], typically what ``search``
+        returned.  -> a dict on the device (``ops.xattn_index_pairs_ground``): ``score`` [Nq, k] (the local addend of the search score, bit
+        for bit), ``word_scores`` / ``word_region`` / ``word_region_weight`` [Nq, k, W], ``region_scores`` / ``region_word`` [Nq, k, G],
+        ``word_valid`` bool [Nq, W] (words of the query that are not padding) and, with ``frames`` (a divisor of G: regions are frame-major),
+        ``frame_scores`` [Nq, k, frames] and ``word_frame`` = ``word_region // (G // frames)``.  Fused route only; no gradient flows."""
+        self._ground_checks(frames)
+        ids_in = text["input_ids"]
+        if not (ids_in.is_cuda and ids.is_cuda):
+            raise DemoVLPHipError("VideoIndex.ground runs on an MI355X device only (no CPU fallback): move the queries and ids to cuda")
+        if ids.dim() != 2 or ids.shape[0] != ids_in.shape[0] or ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"ids must be int [Nq = {ids_in.shape[0]}, k], got {ids.dtype} {tuple(ids.shape)}")
+        if self.n == 0:
+            raise ValueError("the index is empty")
+        was_training = model.training
+        model.eval()
+        res = []
+        try:
+            with torch.no_grad():
+                for q0 in range(0, ids_in.shape[0], QUERY_BLOCK):
+                    block = {name: t[q0:q0 + QUERY_BLOCK] for name, t in text.items() if isinstance(t, torch.Tensor)}
+                    res.append(self._ground_block(loss_fn, self._text_side(model, block), block["attention_mask"], ids[q0:q0 + QUERY_BLOCK], frames))
+        finally:
+            if was_training:
+                model.train()
+        return {name: torch.cat([r[name] for r in res]) for name in res[0]}
+
+    def search(self, model, loss_fn, text, k=10, shortlist=100, chunk=65536, ground=False, frames=None):
         """The ``k`` best videos for every query of ``text`` (``{'input_ids', 'attention_mask'}`` [Nq, L] on the device) ->
         ``(ids int64 [Nq, k], scores fp32 [Nq, k])`` on the device, best first, equal scores by smaller id; ids are index rows.
+        With ``ground=True``: ``(ids, scores, grounding)``, the dict of ``VideoIndex.ground`` for the k winners (one more launch over them,
+        on the text-tower outputs the search used; ``frames`` as there).
 
         ``loss_fn`` supplies ``lambda_softmax`` / ``focal_type`` (a ``GlobalLocalLoss`` or its ``RWALoss``).  ``shortlist``: videos per query
         that reach the local stage, chosen by cosine (at most 1024); ``None`` or ``>= len(index)`` scores every video (exact search).
@@ -194,6 +251,8 @@ class VideoIndex:
             raise ValueError(f"k and a partial shortlist are limited to {TOPK_MAX} (dvlp_topk_rows)")
         if chunk < 1:
             raise ValueError(f"chunk must be positive, got {chunk}")
+        if ground:
+            self._ground_checks(frames)
         ids_in = text["input_ids"]
         if not ids_in.is_cuda:
             raise DemoVLPHipError("VideoIndex.search runs on an MI355X device only (no CPU fallback): move the queries to cuda")
@@ -204,13 +263,18 @@ class VideoIndex:
             with torch.no_grad():
                 for q0 in range(0, ids_in.shape[0], QUERY_BLOCK):
                     block = {name: t[q0:q0 + QUERY_BLOCK] for name, t in text.items() if isinstance(t, torch.Tensor)}
-                    _, ids, cos, local = self._score(model, loss_fn, block, S, chunk)
+                    side = self._text_side(model, block)
+                    _, ids, cos, local = self._score(model, loss_fn, block, S, chunk, side)
                     val, pos = ops.topk_rows(cos + local, k)
-                    res.append((torch.gather(ids, 1, pos.long()).long(), val))
+                    top = torch.gather(ids, 1, pos.long()).long()
+                    res.append((top, val, self._ground_block(loss_fn, side, block["attention_mask"], top, frames) if ground else None))
         finally:
             if was_training:
                 model.train()
-        return torch.cat([r[0] for r in res]), torch.cat([r[1] for r in res])
+        ids, scores = torch.cat([r[0] for r in res]), torch.cat([r[1] for r in res])
+        if not ground:
+            return ids, scores
+        return ids, scores, {name: torch.cat([r[2][name] for r in res]) for name in res[0][2]}
 
 
 def two_stage_sims(global_sims, ids, scores):

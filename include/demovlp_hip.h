@@ -236,6 +236,28 @@ int dvlp_xattn_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, c
                                const void* Qraw, const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores,
                                void* workspace, void* stream);
 
+/* Grounding of the same pairs (no reference counterpart beyond an HTML visualiser every shipped config switches off): the local similarity
+   above (model/loss.py:209-330) of caption j and video cand[j K + k], and where it came from.  One launch on the (K, Bj) grid of
+   dvlp_xattn_index_pairs_fwd running the same per-pair code; in the notation of that score (A = S / |S_row|, A2 = S / |S_col|, P / P2 the
+   two focal softmaxes), per pair o = j K + k:
+     score              fp32 [Bj][K]     equal to dvlp_xattn_index_pairs_fwd's scores[j][k] bit for bit
+     word_scores        fp32 [Bj][K][W]  cos(Q_w, (P C^)_w) for every word, padded ones included; mean over w = the image->text half of score
+     region_scores      fp32 [Bj][K][G]  cos(C_g, (P2 Q^)_g) for every region, masked ones included; mean over g = the other half
+     word_region        int32 [Bj][K][W] argmax over g of lam (A[g][w] + mimg[g]) (ties: smaller g): the region word w attends to most
+     word_region_weight fp32 [Bj][K][W]  P[w][word_region[w]] after the focal gate and renormalisation (the bf16 value the kernel multiplies with)
+     region_word        int32 [Bj][K][G] argmax over w of lam (A2[g][w] + mcap[w]) (ties: smaller w)
+     frame_scores       fp32 [Bj][K][frames]  mean of region_scores over the frame's regions (G / frames consecutive ones) with mimg == 0;
+                                         -inf for a frame without one.  frames = 0 and frame_scores = NULL: not computed.
+   The argmaxes are taken from the fp32 logits and do not depend on scheduling.  A cand entry outside [0, capacity) reads nothing: NaN in the
+   float rows, -1 in the int rows.  Argument errors -- d != 256, frames not dividing G (or frames != 0 without frame_scores and the reverse),
+   K < 1, a null required pointer, a shape outside the fused range (G <= 288, W <= 112) -- return DVLP_ERR_SHAPE and launch nothing.  bf16
+   only.  workspace: dvlp_xattn_index_ground_workspace_bytes(Bj, W, K, G) bytes (host arithmetic; a negative DVLP_ERR_* outside that range). */
+int64_t dvlp_xattn_index_ground_workspace_bytes(int64_t Bj, int64_t W, int64_t K, int64_t G);
+int dvlp_xattn_index_pairs_ground(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                  const void* Qraw, const float* mcap, const int* cand, int64_t K, int64_t frames, float lam, int gate,
+                                  float* score, float* word_scores, float* region_scores, int* word_region, float* word_region_weight,
+                                  int* region_word, float* frame_scores, void* workspace, void* stream);
+
 /* ---- row top-k (csrc/topk.hip; no reference counterpart: the reference ranks on the host, model/metric.py) ----
    Per row m of the fp32 matrix x [M][ld] (first N columns): val[m][0..K) = the K largest values, descending, idx[m][..] = their column numbers
    + index_base (int32).  Total order: larger value first, equal values by smaller index -- np.argsort(-x, kind="stable")[:K]; -0.0 == +0.0; a NaN
