@@ -1621,6 +1621,83 @@ extern "C" int dvlp_xattn_index_pairs_ground(int64_t capacity, int64_t G, const 
     return dvlp_launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// resident caption index (video-to-text search): the family above with the roles swapped -- the fused kernel's prepared CAPTION side kept by
+// the caller, and the video-major pair list over it: scores[i][k] = local similarity of video i and caption cand[i K + k] of the index.
+// bf16, fused range only (xfused.hip).
+// ------------------------------------------------------------------------------------------------------------------
+int64_t dvlp_xfused_caption_index_bytes(int64_t capacity, int64_t W);
+int64_t dvlp_xfused_video_query_bytes(int64_t Bi, int64_t G);
+int dvlp_xfused_caption_index_add(int64_t capacity, int64_t W, int64_t row0, int64_t n, const void* Qraw, void* index, hipStream_t st);
+int dvlp_xfused_caption_index_pairs_fwd(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G, const void* Craw,
+                                        const float* mimg, int64_t K, const int* cand, float lam, int gate, float* scores, void* workspace,
+                                        hipStream_t st);
+int dvlp_xfused_caption_index_pairs_ground(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G,
+                                           const void* Craw, const float* mimg, int64_t K, const int* cand, int frames, float lam, int gate,
+                                           float* scores, float* word_scores, float* region_scores, int* word_region, float* word_weight,
+                                           int* region_word, float* frame_scores, void* workspace, hipStream_t st);
+
+extern "C" int64_t dvlp_xattn_caption_index_bytes(int64_t capacity, int64_t W) {
+    if (capacity <= 0 || capacity > INT32_MAX || W <= 0) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(1, W)) return DVLP_ERR_UNSUPPORTED;         // (W <= 112; the region count is a query call's)
+    return dvlp_xfused_caption_index_bytes(capacity, W);
+}
+
+extern "C" int dvlp_xattn_caption_index_add(int64_t capacity, int64_t W, int64_t row0, int64_t n, const void* Qraw, void* index, void* stream) {
+    dvlp_clear_status();
+    if (capacity <= 0 || capacity > INT32_MAX || W <= 0 || row0 < 0 || n <= 0 || row0 + n > capacity) return DVLP_ERR_SHAPE;
+    if (!Qraw || !index) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(1, W)) return DVLP_ERR_UNSUPPORTED;
+    dvlp_xfused_caption_index_add(capacity, W, row0, n, Qraw, index, (hipStream_t)stream);
+    return dvlp_launch_status();
+}
+
+extern "C" int64_t dvlp_xattn_caption_index_query_workspace_bytes(int64_t Bi, int64_t G, int64_t W) {
+    if (Bi <= 0 || G <= 0 || W <= 0 || Bi > 65535) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    return dvlp_xfused_video_query_bytes(Bi, G);
+}
+
+extern "C" int dvlp_xattn_caption_index_pairs_fwd(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G,
+                                                  int64_t d, const void* Craw, const float* mimg, int64_t K, const int* cand, float lam, int gate,
+                                                  float* scores, void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != XD || capacity <= 0 || capacity > INT32_MAX || W <= 0 || Bi <= 0 || G <= 0 || K <= 0) return DVLP_ERR_SHAPE;
+    if (Bi > 65535 || Bi * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mcap || !Craw || !mimg || !cand || !scores || !workspace) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    dvlp_xfused_caption_index_pairs_fwd(capacity, W, index, mcap, Bi, G, Craw, mimg, K, cand, lam, gate & 1, scores, workspace, (hipStream_t)stream);
+    return dvlp_launch_status();
+}
+
+// grounding of the pairs of dvlp_xattn_caption_index_pairs_fwd: the same score (bit for bit) plus where it came from.  Anything wrong with
+// the arguments, a shape beyond the fused range included, is DVLP_ERR_SHAPE; nothing is launched then.
+extern "C" int64_t dvlp_xattn_caption_index_ground_workspace_bytes(int64_t Bi, int64_t G, int64_t K, int64_t W) {
+    if (Bi <= 0 || G <= 0 || K <= 0 || W <= 0 || Bi > 65535 || Bi * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    return dvlp_xfused_video_query_bytes(Bi, G);                    // the video-side prep; the cross-wave exchange lives in dead LDS
+}
+
+extern "C" int dvlp_xattn_caption_index_pairs_ground(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G,
+                                                     int64_t d, const void* Craw, const float* mimg, const int* cand, int64_t K, int64_t frames,
+                                                     float lam, int gate, float* score, float* word_scores, float* region_scores,
+                                                     int* word_region, float* word_region_weight, int* region_word, float* frame_scores,
+                                                     void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != XD || capacity <= 0 || capacity > INT32_MAX || W <= 0 || Bi <= 0 || G <= 0 || K < 1) return DVLP_ERR_SHAPE;
+    if (Bi > 65535 || Bi * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mcap || !Craw || !mimg || !cand || !score || !word_scores || !region_scores || !word_region || !word_region_weight ||
+        !region_word || !workspace)
+        return DVLP_ERR_SHAPE;
+    // frames = 0 <=> no frame_scores; otherwise frames must divide G
+    if (frames < 0 || frames > G || (frames == 0) != (frame_scores == nullptr) || (frames > 0 && G % frames != 0)) return DVLP_ERR_SHAPE;
+    if (!dvlp_xfused_ok(G, W)) return DVLP_ERR_SHAPE;
+    dvlp_xfused_caption_index_pairs_ground(capacity, W, index, mcap, Bi, G, Craw, mimg, K, cand, (int)frames, lam, gate & 1, score, word_scores,
+                                           region_scores, word_region, word_region_weight, region_word, frame_scores, workspace,
+                                           (hipStream_t)stream);
+    return dvlp_launch_status();
+}
+
 // workspace must be the one dvlp_xattn_fwd(..., bwd=1) filled.  Outputs: dC [Bi][G][d], dQ [Bj][W][d] (compute dtype).
 extern "C" int dvlp_xattn_bwd(int dtype, int64_t Bi, int64_t Bj, int64_t G, int64_t W, int64_t d, const void* Craw, const void* Qraw,
                               const float* mimg, const float* mcap, float lam, int gate, const float* dscores, void* workspace,

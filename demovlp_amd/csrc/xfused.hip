@@ -666,6 +666,43 @@ __global__ __launch_bounds__(512) void xf_index_pairs_ground_kernel(FusedArgs a,
     xf_pair_score<true>(a, smem, i, j, a.scores + o, go);
 }
 
+// resident CAPTION index, video-major pair list (the roles of xf_index_pairs_kernel swapped): workgroup (k, i) -> scores[i][k], caption
+// cand[i K + k] of the index (a.Bj = its capacity), video i of the per-call workspace; an index outside [0, capacity) reads nothing and
+// scores NaN
+__global__ __launch_bounds__(512) void xf_caption_index_pairs_kernel(FusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int i = blockIdx.y;
+    const int64_t o = (int64_t)i * a.K + blockIdx.x;
+    const int j = a.cand[o];
+    if (j < 0 || j >= a.Bj) {
+        if (threadIdx.x == 0) a.scores[o] = __builtin_nanf("");
+        return;
+    }
+    xf_pair_score<false>(a, smem, i, j, a.scores + o, GroundOut{});
+}
+
+// the same grid with grounding: `go` holds the bases of the [Bi][K][...] output arrays; pair o = i K + k writes row o of each.  An index
+// outside [0, capacity) reads nothing: NaN in the float rows, -1 in the int rows.
+__global__ __launch_bounds__(512) void xf_caption_index_pairs_ground_kernel(FusedArgs a, GroundOut go) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int i = blockIdx.y;
+    const int64_t o = (int64_t)i * a.K + blockIdx.x;
+    const int j = a.cand[o];
+    go.word_scores += o * a.W; go.word_region += o * a.W; go.word_weight += o * a.W;
+    go.region_scores += o * a.G; go.region_word += o * a.G;
+    if (go.frame_scores) go.frame_scores += o * go.frames;
+    if (j < 0 || j >= a.Bj) {
+        const float nan = __builtin_nanf("");
+        if (threadIdx.x == 0) a.scores[o] = nan;
+        for (int t = threadIdx.x; t < a.W; t += blockDim.x) { go.word_scores[t] = nan; go.word_weight[t] = nan; go.word_region[t] = -1; }
+        for (int t = threadIdx.x; t < a.G; t += blockDim.x) { go.region_scores[t] = nan; go.region_word[t] = -1; }
+        if (go.frame_scores)
+            for (int t = threadIdx.x; t < go.frames; t += blockDim.x) go.frame_scores[t] = nan;
+        return;
+    }
+    xf_pair_score<true>(a, smem, i, j, a.scores + o, go);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // host side (called from dvlp_xattn_fwd / dvlp_xattn_bwd in xattn.hip)
 // ------------------------------------------------------------------------------------------------------------------
@@ -817,5 +854,70 @@ int dvlp_xfused_index_pairs_ground(int64_t capacity, int64_t G, const void* inde
     { static bool once = false; if (!once) { once = true;
         (void)hipFuncSetAttribute((const void*)xf_index_pairs_ground_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
     hipLaunchKernelGGL(xf_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bj), dim3(512), (size_t)L.total, st, a, go);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// resident caption side (dvlp_xattn_caption_index_*): the roles of the family above swapped.  Per caption the index holds what xf_prep
+// writes per call -- qhat [Wp][256], qhatT [256][Wk] (bf16), nq [W] (fp32) -- for `capacity` captions of W words, filled `n` rows at a
+// time by the same prep kernel; a query call then preps its Bi videos only (chat, chatT, nc: the sections of IndexLayout at capacity Bi).
+// ------------------------------------------------------------------------------------------------------------------
+int64_t dvlp_xfused_caption_index_bytes(int64_t capacity, int64_t W) { return query_layout(capacity, W).total; }
+int64_t dvlp_xfused_video_query_bytes(int64_t Bi, int64_t G) { return index_layout(Bi, G).total; }
+
+int dvlp_xfused_caption_index_add(int64_t capacity, int64_t W, int64_t row0, int64_t n, const void* Qraw, void* index, hipStream_t st) {
+    const QueryLayout Q = query_layout(capacity, W);
+    char* ix = (char*)index;
+    const int64_t rq = Q.Wp > Q.Wk ? Q.Wp : Q.Wk;
+    hipLaunchKernelGGL(xf_prep_kernel, dim3((unsigned)cdiv(n * rq, 4)), dim3(256), 0, st, (int)n, (int)W, (int)Q.Wp, (int)Q.Wk, (const bf16*)Qraw,
+                       (bf16*)(ix + Q.off_qhat) + row0 * Q.Wp * FD, (bf16*)(ix + Q.off_qhatT) + row0 * FD * Q.Wk, (float*)(ix + Q.off_nq) + row0 * W);
+    return 0;
+}
+
+// prep of the Bi videos into the workspace; the kernel arguments of the caption-index pair kernels
+static FusedArgs xf_caption_index_prep(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G, const void* Craw,
+                                       const float* mimg, int64_t K, const int* cand, float lam, int gate, float* scores, void* workspace,
+                                       hipStream_t st) {
+    const QueryLayout Q = query_layout(capacity, W);
+    const IndexLayout I = index_layout(Bi, G);
+    const char* ix = (const char*)index;
+    char* ws = (char*)workspace;
+    FusedArgs a{};
+    a.qhat = (const bf16*)(ix + Q.off_qhat); a.qhatT = (const bf16*)(ix + Q.off_qhatT); a.nq = (const float*)(ix + Q.off_nq);
+    a.chat = (const bf16*)(ws + I.off_chat); a.chatT = (const bf16*)(ws + I.off_chatT); a.nc = (const float*)(ws + I.off_nc);
+    a.mimg = mimg; a.mcap = mcap; a.scores = scores; a.cand = cand; a.K = (int)K;
+    a.Bi = (int)Bi; a.Bj = (int)capacity; a.G = (int)G; a.W = (int)W; a.Gr = (int)I.Gr; a.Gk = (int)I.Gk; a.Wp = (int)Q.Wp; a.Wk = (int)Q.Wk;
+    a.lam = lam; a.gate = gate; a.stop = g_xf_stop;
+    const int64_t rc = I.Gr > I.Gk ? I.Gr : I.Gk;
+    hipLaunchKernelGGL(xf_prep_kernel, dim3((unsigned)cdiv(Bi * rc, 4)), dim3(256), 0, st, (int)Bi, (int)G, (int)I.Gr, (int)I.Gk, (const bf16*)Craw,
+                       (bf16*)(ws + I.off_chat), (bf16*)(ws + I.off_chatT), (float*)(ws + I.off_nc));
+    return a;
+}
+
+int dvlp_xfused_caption_index_pairs_fwd(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G, const void* Craw,
+                                        const float* mimg, int64_t K, const int* cand, float lam, int gate, float* scores, void* workspace,
+                                        hipStream_t st) {
+    const FusedArgs a = xf_caption_index_prep(capacity, W, index, mcap, Bi, G, Craw, mimg, K, cand, lam, gate, scores, workspace, st);
+    const FLds L = flds(a.Gr, a.Gk, a.Wp, a.Wk);
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xf_caption_index_pairs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xf_caption_index_pairs_kernel, dim3((unsigned)K, (unsigned)Bi), dim3(512), (size_t)L.total, st, a);
+    return 0;
+}
+
+// grounding of the same pairs (dvlp_xattn_caption_index_pairs_ground): the same prep and grid; no ablation switch reaches it
+int dvlp_xfused_caption_index_pairs_ground(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G,
+                                           const void* Craw, const float* mimg, int64_t K, const int* cand, int frames, float lam, int gate,
+                                           float* scores, float* word_scores, float* region_scores, int* word_region, float* word_weight,
+                                           int* region_word, float* frame_scores, void* workspace, hipStream_t st) {
+    FusedArgs a = xf_caption_index_prep(capacity, W, index, mcap, Bi, G, Craw, mimg, K, cand, lam, gate, scores, workspace, st);
+    a.stop = 0;
+    GroundOut go{};
+    go.word_scores = word_scores; go.region_scores = region_scores; go.word_region = word_region; go.region_word = region_word;
+    go.word_weight = word_weight; go.frame_scores = frame_scores; go.frames = frames;
+    const FLds L = flds(a.Gr, a.Gk, a.Wp, a.Wk);
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xf_caption_index_pairs_ground_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xf_caption_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bi), dim3(512), (size_t)L.total, st, a, go);
     return 0;
 }

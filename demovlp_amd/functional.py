@@ -686,6 +686,21 @@ class XattnIndexPairsFn(torch.autograd.Function):
         raise ops._lib.DemoVLPHipError("the index pair-list local similarity (dvlp_xattn_index_pairs_fwd) is forward only: it has no backward")
 
 
+class XattnCaptionIndexPairsFn(torch.autograd.Function):
+    """xattn_score_fast of video i against the captions cand[i, k] of a resident caption index (ops.xattn_caption_index_add): [n_video, K]
+    scores.  Forward only (search); a backward through it raises."""
+
+    @staticmethod
+    def forward(ctx, index, capacity, W, s_m, im, im_m, cand, lam, gate):
+        return ops.xattn_caption_index_pairs_fwd(index, capacity, W, s_m.contiguous().float(), im.contiguous(), im_m.contiguous().float(),
+                                                 cand.contiguous(), lam, gate)
+
+    @staticmethod
+    def backward(ctx, dscores):
+        raise ops._lib.DemoVLPHipError("the caption-index pair-list local similarity (dvlp_xattn_caption_index_pairs_fwd) is forward only: "
+                                       "it has no backward")
+
+
 class RWATailFn(torch.autograd.Function):
     """model/loss.py:105-116 on a given score matrix."""
 

@@ -847,6 +847,84 @@ def xattn_index_pairs_ground(index, capacity, G, m_img, Q, m_cap, cand, lam, gat
     return out
 
 
+def xattn_caption_index_bytes(capacity, W):
+    """Bytes of the prepared (resident) caption side of ``capacity`` captions of W words each; raises outside the fused kernel's range."""
+    return _size("dvlp_xattn_caption_index_bytes", int(capacity), int(W))
+
+
+def _contiguous(**tensors):
+    for name, t in tensors.items():
+        if not t.is_contiguous():
+            raise _lib.DemoVLPHipError(f"{name} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}")
+
+
+def xattn_caption_index_add(index, capacity, W, row0, Q):
+    """Prepare the captions Q (bf16 [n, W, 256]) into rows row0 .. row0 + n of ``index`` (uint8 [xattn_caption_index_bytes(capacity, W)])."""
+    if Q.dtype != torch.bfloat16:
+        raise _lib.DemoVLPHipError(f"the resident caption index is bf16 only, got {Q.dtype}")
+    if Q.dim() != 3 or Q.shape[1] != W or Q.shape[2] != 256:
+        raise _lib.DemoVLPHipError(f"expected Q [n, {W}, 256], got {tuple(Q.shape)}")
+    if index.numel() * index.element_size() < xattn_caption_index_bytes(capacity, W):
+        raise _lib.DemoVLPHipError("index buffer smaller than dvlp_xattn_caption_index_bytes(capacity, W)")
+    _contiguous(index=index, Q=Q)
+    require_gpu(index, Q)
+    call("dvlp_xattn_caption_index_add", int(capacity), int(W), int(row0), Q.shape[0], p(Q), p(index), stream())
+
+
+def _caption_index_checks(index, capacity, W, m_cap, C, m_img, cand):
+    if C.dtype != torch.bfloat16:
+        raise _lib.DemoVLPHipError(f"the resident caption index is bf16 only, got {C.dtype}")
+    if C.dim() != 3 or C.shape[2] != 256:
+        raise _lib.DemoVLPHipError(f"expected C [Bi, G, 256], got {tuple(C.shape)}")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != C.shape[0]:
+        raise _lib.DemoVLPHipError(f"cand must be int32 [Bi, K], got {cand.dtype} {tuple(cand.shape)}")
+    if tuple(m_cap.shape) != (capacity, W) or tuple(m_img.shape) != tuple(C.shape[:2]):
+        raise _lib.DemoVLPHipError(f"masks must be [capacity, W] and [Bi, G], got {tuple(m_cap.shape)} and {tuple(m_img.shape)}")
+    if m_cap.dtype != torch.float32 or m_img.dtype != torch.float32:
+        raise _lib.DemoVLPHipError(f"masks must be fp32, got {m_cap.dtype} and {m_img.dtype}")
+    if index.numel() * index.element_size() < xattn_caption_index_bytes(capacity, W):
+        raise _lib.DemoVLPHipError("index buffer smaller than dvlp_xattn_caption_index_bytes(capacity, W)")
+    _contiguous(index=index, m_cap=m_cap, C=C, m_img=m_img, cand=cand)
+    require_gpu(index, m_cap, C, m_img, cand)
+
+
+def xattn_caption_index_pairs_fwd(index, capacity, W, m_cap, C, m_img, cand, lam, gate):
+    """index: prepared captions (xattn_caption_index_add), m_cap fp32 [capacity, W]; C bf16 [Bi, G, 256], m_img fp32 [Bi, G]; cand int32 [Bi, K]
+    caption rows -> scores fp32 [Bi, K] of the pairs (i, cand[i, k]); an entry of cand outside [0, capacity) scores NaN.  Forward only."""
+    _caption_index_checks(index, capacity, W, m_cap, C, m_img, cand)
+    Bi, G, d = C.shape
+    K = cand.shape[1]
+    ws = torch.empty(_size("dvlp_xattn_caption_index_query_workspace_bytes", Bi, G, int(W)), device=C.device, dtype=torch.uint8)
+    scores = torch.empty((Bi, K), device=C.device, dtype=torch.float32)
+    call("dvlp_xattn_caption_index_pairs_fwd", int(capacity), int(W), p(index), p(m_cap), Bi, G, d, p(C), p(m_img), K, p(cand), float(lam),
+         _gate_bits(gate) & 1, p(scores), p(ws), stream())
+    return scores
+
+
+def xattn_caption_index_pairs_ground(index, capacity, W, m_cap, C, m_img, cand, lam, gate, frames=None):
+    """The pairs of ``xattn_caption_index_pairs_fwd`` with their grounding (``dvlp_xattn_caption_index_pairs_ground``, same arguments): the
+    dict of ``xattn_index_pairs_ground`` laid out per (video, k) -- ``score`` fp32 [Bi, K] (bit-equal to ``xattn_caption_index_pairs_fwd``),
+    ``word_scores`` / ``word_region`` / ``word_region_weight`` [Bi, K, W], ``region_scores`` / ``region_word`` [Bi, K, G] and, with ``frames``
+    (a divisor of G), ``frame_scores`` fp32 [Bi, K, frames].  An entry of cand outside [0, capacity) gives NaN / -1 rows.  Forward only."""
+    if frames is not None and (C.dim() != 3 or int(frames) < 1 or C.shape[1] % int(frames) != 0):
+        raise _lib.DemoVLPHipError(f"frames = {frames} must be a positive divisor of G = {C.shape[1] if C.dim() == 3 else None}")
+    _caption_index_checks(index, capacity, W, m_cap, C, m_img, cand)
+    Bi, G, d = C.shape
+    K = cand.shape[1]
+    F = 0 if frames is None else int(frames)
+    ws = torch.empty(_size("dvlp_xattn_caption_index_ground_workspace_bytes", Bi, G, K, int(W)), device=C.device, dtype=torch.uint8)
+    new = lambda n, dtype: torch.empty((Bi, K, n), device=C.device, dtype=dtype)
+    out = dict(score=torch.empty((Bi, K), device=C.device, dtype=torch.float32), word_scores=new(W, torch.float32),
+               region_scores=new(G, torch.float32), word_region=new(W, torch.int32), word_region_weight=new(W, torch.float32),
+               region_word=new(G, torch.int32))
+    if F:
+        out["frame_scores"] = new(F, torch.float32)
+    call("dvlp_xattn_caption_index_pairs_ground", int(capacity), int(W), p(index), p(m_cap), Bi, G, d, p(C), p(m_img), p(cand), K, F, float(lam),
+         _gate_bits(gate) & 1, p(out["score"]), p(out["word_scores"]), p(out["region_scores"]), p(out["word_region"]),
+         p(out["word_region_weight"]), p(out["region_word"]), p(out["frame_scores"]) if F else None, p(ws), stream())
+    return out
+
+
 def topk_rows(x, K, N=None, index_base=0, out=None, merge=False):
     """x fp32 [M, ld] (first N columns; default all) -> (val fp32 [M, K], idx int32 [M, K]): per row the K largest values in descending order,
     ties by smaller index (np.argsort(-x, kind="stable")[:, :K] + index_base), NaN last, (-inf, -1) where N < K.  ``out`` = (val, idx) to write

@@ -20,6 +20,14 @@ the reference's quirk of adding the global [text, video] and local [video, text]
 (trainer/trainer_dist.py:369-399); search does not.  In ``evaluate``'s terms the search score is ``global_sims + local_sims.T``, and metrics
 computed from search results (``evaluate_t2v``) are NOT comparable with the reference's evaluation numbers.
 
+Video-to-text search is the same pipeline with the roles swapped.  ``CaptionIndex`` keeps a collection of captions (tags, descriptions)
+resident -- normalised global text embeddings, additive word masks and the caption side of the fused kernel (``dvlp_xattn_caption_index_add``:
+123 392 bytes per caption at W = 99) -- and ``CaptionIndex.search`` answers "which captions fit this clip": object tower, cosine shortlist,
+``dvlp_xattn_caption_index_pairs_fwd`` over the shortlist, final top-k; ``CaptionIndex.ground`` grounds the winners.  The pair score is the
+one above, ``cos(video_i, text_j) + local(video_i, caption_j)``, so an exact v2t search is the transpose of an exact t2v search: in
+``evaluate``'s terms ``global_sims.T + local_sims``, again not the quirk matrix, and ``evaluate_v2t`` is no more comparable with the
+reference's numbers than ``evaluate_t2v``.
+
 fp32 models, and region counts beyond the fused kernel's range (G > 288), take the parity route: the raw local embeddings are kept and each
 query's shortlist is gathered and scored by the multi-kernel ``RWALoss.get_sim`` -- slow and exact, as fp32 is everywhere in this package.
 """
@@ -35,9 +43,53 @@ from ._lib import DemoVLPHipError, call
 _DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16, torch.float32: torch.float32, torch.bfloat16: torch.bfloat16}
 TOPK_MAX = 1024               # dvlp_topk_rows: 1 <= K <= 1024
 QUERY_BLOCK = 1024            # queries per pass of the pipeline (bounds the text tower's and the pair kernel's scratch)
+VIDEO_BLOCK = 256             # query videos per pass of CaptionIndex's pipeline (the object tower runs G + 1 tokens per video, not 100)
 
 
-class VideoIndex:
+class _ResidentIndex:
+    """What both directions share: the row count, the search-argument checks and the global (cosine) stage over ``self.gn`` [capacity, 256],
+    the normalised global embeddings of the ``self.n`` resident rows."""
+
+    def __len__(self):
+        return self.n
+
+    def _shortlist_size(self, shortlist):
+        return self.n if shortlist is None or shortlist >= self.n else int(shortlist)
+
+    def _search_checks(self, k, shortlist, chunk):
+        """-> (k, S, chunk) of a search call, or the ValueError that names what is wrong with them"""
+        k, chunk = int(k), int(chunk)
+        if self.n == 0:
+            raise ValueError("the index is empty")
+        S = self._shortlist_size(shortlist)
+        if k < 1 or k > S:
+            raise ValueError(f"k = {k} must lie in [1, shortlist = {S}]")
+        if k > TOPK_MAX or (S < self.n and S > TOPK_MAX):
+            raise ValueError(f"k and a partial shortlist are limited to {TOPK_MAX} (dvlp_topk_rows)")
+        if chunk < 1:
+            raise ValueError(f"chunk must be positive, got {chunk}")
+        return k, S, chunk
+
+    def _global_stage(self, qn, S, chunk):
+        """-> (ids int32 [Nq, S] ascending per row, cosines fp32 [Nq, S]) of the S best index rows per query by cosine."""
+        Nq, dev = qn.shape[0], qn.device
+        if S == self.n:                                            # every row: nothing to select
+            cos = torch.empty((Nq, self.n), device=dev, dtype=torch.float32)
+            for c0 in range(0, self.n, chunk):
+                cn = min(chunk, self.n - c0)
+                ops.gemm(qn, self.gn[c0:], Nq, cn, 256, dtype=ops.F32, out=cos[:, c0:], ldc=self.n)
+            return torch.arange(self.n, device=dev, dtype=torch.int32).expand(Nq, -1).contiguous(), cos
+        out = (torch.empty((Nq, S), device=dev, dtype=torch.float32), torch.empty((Nq, S), device=dev, dtype=torch.int32))
+        for c0 in range(0, self.n, chunk):
+            cn = min(chunk, self.n - c0)
+            sims = ops.gemm(qn, self.gn[c0:], Nq, cn, 256, dtype=ops.F32)
+            ops.topk_rows(sims, S, index_base=c0, out=out, merge=c0 > 0)
+        # by id: the final cut breaks score ties by position in the shortlist, which must then mean "smaller id first"
+        ids, order = torch.sort(out[1], dim=1)
+        return ids.contiguous(), torch.gather(out[0], 1, order).contiguous()
+
+
+class VideoIndex(_ResidentIndex):
     """A collection of videos prepared for search.  ``capacity`` videos of ``G`` regions (frames x regions per frame) in the model's compute
     ``dtype``; device memory is allocated at the first ``add``."""
 
@@ -51,9 +103,6 @@ class VideoIndex:
         # fused route: bf16 within the fused kernel's range (host arithmetic; a negative size is "not supported")
         self.fused = self.dtype == torch.bfloat16 and call("dvlp_xattn_index_bytes", self.capacity, self.G) > 0
         self.gn = self.om = self.local = None
-
-    def __len__(self):
-        return self.n
 
     def _alloc(self):
         if self.gn is not None:
@@ -126,9 +175,6 @@ class VideoIndex:
         return self
 
     # ---- search -------------------------------------------------------------------------------------------------------
-    def _shortlist_size(self, shortlist):
-        return self.n if shortlist is None or shortlist >= self.n else int(shortlist)
-
     def shortlist_by_cosine(self, global_text_embeddings, shortlist, chunk=65536):
         """The global stage alone: (ids int64 [Nq, S] ascending per row, cosines fp32 [Nq, S]) of the ``shortlist`` best videos per query
         embedding [Nq, 256] by cosine (ties by smaller id)."""
@@ -137,24 +183,6 @@ class VideoIndex:
         with torch.no_grad():
             ids, cos = self._global_stage(ops.rownorm_fwd(global_text_embeddings.detach().contiguous())[0], self._shortlist_size(shortlist), int(chunk))
         return ids.long(), cos
-
-    def _global_stage(self, qn, S, chunk):
-        """-> (ids int32 [Nq, S] ascending per row, cosines fp32 [Nq, S]) of the S best videos per query by cosine."""
-        Nq, dev = qn.shape[0], qn.device
-        if S == self.n:                                            # every video: nothing to select
-            cos = torch.empty((Nq, self.n), device=dev, dtype=torch.float32)
-            for c0 in range(0, self.n, chunk):
-                cn = min(chunk, self.n - c0)
-                ops.gemm(qn, self.gn[c0:], Nq, cn, 256, dtype=ops.F32, out=cos[:, c0:], ldc=self.n)
-            return torch.arange(self.n, device=dev, dtype=torch.int32).expand(Nq, -1).contiguous(), cos
-        out = (torch.empty((Nq, S), device=dev, dtype=torch.float32), torch.empty((Nq, S), device=dev, dtype=torch.int32))
-        for c0 in range(0, self.n, chunk):
-            cn = min(chunk, self.n - c0)
-            sims = ops.gemm(qn, self.gn[c0:], Nq, cn, 256, dtype=ops.F32)
-            ops.topk_rows(sims, S, index_base=c0, out=out, merge=c0 > 0)
-        # by id: the final cut breaks score ties by position in the shortlist, which must then mean "smaller id first"
-        ids, order = torch.sort(out[1], dim=1)
-        return ids.contiguous(), torch.gather(out[0], 1, order).contiguous()
 
     def _local_stage(self, local_loss, lt, text_mask, ids):
         lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
@@ -241,16 +269,7 @@ class VideoIndex:
         ``chunk``: index rows per global-stage product.  The score is ``cos(text_j, video_i) + local(video_i, caption_j)``: in
         ``trainer.evaluate``'s terms ``global_sims + local_sims.T``, NOT its ``o2t_sims`` (which keeps the reference's transposed-addend
         quirk), so metrics of search results are not comparable with the reference's evaluation numbers.  No gradient flows."""
-        k, chunk = int(k), int(chunk)
-        if self.n == 0:
-            raise ValueError("the index is empty")
-        S = self._shortlist_size(shortlist)
-        if k < 1 or k > S:
-            raise ValueError(f"k = {k} must lie in [1, shortlist = {S}]")
-        if k > TOPK_MAX or (S < self.n and S > TOPK_MAX):
-            raise ValueError(f"k and a partial shortlist are limited to {TOPK_MAX} (dvlp_topk_rows)")
-        if chunk < 1:
-            raise ValueError(f"chunk must be positive, got {chunk}")
+        k, S, chunk = self._search_checks(k, shortlist, chunk)
         if ground:
             self._ground_checks(frames)
         ids_in = text["input_ids"]
@@ -268,6 +287,229 @@ class VideoIndex:
                     val, pos = ops.topk_rows(cos + local, k)
                     top = torch.gather(ids, 1, pos.long()).long()
                     res.append((top, val, self._ground_block(loss_fn, side, block["attention_mask"], top, frames) if ground else None))
+        finally:
+            if was_training:
+                model.train()
+        ids, scores = torch.cat([r[0] for r in res]), torch.cat([r[1] for r in res])
+        if not ground:
+            return ids, scores
+        return ids, scores, {name: torch.cat([r[2][name] for r in res]) for name in res[0][2]}
+
+
+class CaptionIndex(_ResidentIndex):
+    """A collection of captions (tags, descriptions) prepared for video-to-text search.  ``capacity`` captions of exactly ``W`` words (the
+    tokenised length minus the CLS position) in the model's compute ``dtype``; device memory is allocated at the first ``add``.
+
+    Resident: the normalised global text embeddings ``gn`` [capacity, 256], the additive word masks ``tm`` [capacity, W] and the caption side
+    of the fused local-similarity kernel exactly as that kernel reads it (``dvlp_xattn_caption_index_add``: 123 392 bytes per caption at
+    W = 99).  bf16 with W <= 112 is the ``fused`` route; anything else keeps the raw embeddings [capacity, W, 256] and scores each query
+    video's shortlist with ``RWALoss.get_sim`` on a [1, S] grid (the parity route: exact and slow)."""
+
+    def __init__(self, capacity, W, dtype=torch.bfloat16, device="cuda"):
+        if int(capacity) < 1 or int(W) < 1:
+            raise ValueError(f"capacity and W must be positive, got {capacity} and {W}")
+        if dtype not in _DTYPES:
+            raise ValueError(f"dtype must be float32 or bfloat16, got {dtype!r}")
+        self.capacity, self.W, self.dtype, self.device = int(capacity), int(W), _DTYPES[dtype], torch.device(device)
+        self.n = 0
+        # fused route: bf16 within the fused kernel's range (host arithmetic; a negative size is "not supported")
+        self.fused = self.dtype == torch.bfloat16 and call("dvlp_xattn_caption_index_bytes", self.capacity, self.W) > 0
+        self.gn = self.tm = self.local = None
+
+    def _alloc(self):
+        if self.gn is not None:
+            return
+        if self.device.type != "cuda":
+            raise DemoVLPHipError("CaptionIndex lives on an MI355X device only (no CPU fallback)")
+        dev = self.device
+        self.gn = torch.zeros((self.capacity, 256), device=dev, dtype=torch.float32)
+        self.tm = torch.zeros((self.capacity, self.W), device=dev, dtype=torch.float32)
+        if self.fused:      # zeroed: the alignment gaps between its sections are never written, and the buffer is compared / saved as bytes
+            self.local = torch.zeros(ops.xattn_caption_index_bytes(self.capacity, self.W), device=dev, dtype=torch.uint8)
+        else:
+            self.local = torch.zeros((self.capacity, self.W, 256), device=dev, dtype=self.dtype)
+
+    # ---- filling ------------------------------------------------------------------------------------------------------
+    def add(self, global_text, local_text, attention_mask):
+        """Append captions from the text tower's outputs (``model.compute_text``): ``global_text`` [n, 256], ``local_text`` [n, W, 256] and
+        the tokeniser's ``attention_mask`` [n, W + 1] (CLS position first).  Exactly ``W`` words: another width raises ``ValueError`` -- the
+        text tower's bf16 output depends on the shape it ran at, so padding here would break bit-equality with the full grid.  Returns the
+        index rows they took."""
+        gt, lt, att = global_text, local_text, attention_mask
+        n = gt.shape[0]
+        if lt.dim() != 3 or lt.shape[1] != self.W or lt.shape[2] != 256:
+            raise ValueError(f"this index holds captions of W = {self.W} words: expected local embeddings [n, {self.W}, 256], got {tuple(lt.shape)}")
+        if tuple(gt.shape) != (n, 256) or lt.shape[0] != n or tuple(att.shape) != (n, self.W + 1):
+            raise ValueError(f"expected [n, 256], [n, {self.W}, 256], [n, {self.W + 1}], got {tuple(gt.shape)}, {tuple(lt.shape)}, {tuple(att.shape)}")
+        if lt.dtype != self.dtype:
+            raise ValueError(f"this index holds {self.dtype} embeddings, got {lt.dtype}")
+        if self.n + n > self.capacity:
+            raise ValueError(f"adding {n} captions to {self.n} exceeds the capacity {self.capacity}")
+        if not (gt.is_cuda and lt.is_cuda and att.is_cuda):
+            raise DemoVLPHipError("CaptionIndex lives on an MI355X device only (no CPU fallback): embeddings must be on the device")
+        self._alloc()
+        r0 = self.n
+        with torch.no_grad():
+            self.gn[r0:r0 + n] = ops.rownorm_fwd(gt.detach().contiguous())[0]
+            self.tm[r0:r0 + n] = ((att[:, 1:].contiguous() - 1.0) * 100.0).float()      # as trainer.evaluate (trainer/trainer_dist.py:156-159)
+            if self.fused:
+                ops.xattn_caption_index_add(self.local, self.capacity, self.W, r0, lt.detach().contiguous())
+            else:
+                self.local[r0:r0 + n] = lt.detach()
+        self.n += n
+        return range(r0, r0 + n)
+
+    def add_batches(self, model, batches):
+        """Run the text tower only (``model.compute_text``) on every batch (``{'text': {'input_ids', 'attention_mask'}, ...}`` or the text
+        dict itself) in eval mode and add its captions; the model's training flag is restored."""
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                for data in batches:
+                    text = data["text"] if "text" in data else data
+                    gt, lt = model.compute_text(text)
+                    self.add(gt, lt, text["attention_mask"])
+        finally:
+            if was_training:
+                model.train()
+        return self
+
+    # ---- persistence --------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        self._alloc()
+        return dict(capacity=self.capacity, W=self.W, dtype=str(self.dtype).replace("torch.", ""), n=self.n, fused=self.fused,
+                    gn=self.gn.cpu(), tm=self.tm.cpu(), local=self.local.cpu())
+
+    def load_state_dict(self, state):
+        if (state["capacity"], state["W"], _DTYPES[state["dtype"]], bool(state["fused"])) != (self.capacity, self.W, self.dtype, self.fused):
+            raise ValueError("state_dict belongs to an index of another capacity / W / dtype")
+        self._alloc()
+        for name in ("gn", "tm", "local"):
+            getattr(self, name).copy_(state[name])
+        self.n = int(state["n"])
+        return self
+
+    # ---- search -------------------------------------------------------------------------------------------------------
+    def shortlist_by_cosine(self, global_object_embeddings, shortlist, chunk=65536):
+        """The global stage alone: (ids int64 [Nv, S] ascending per row, cosines fp32 [Nv, S]) of the ``shortlist`` best captions per video
+        embedding [Nv, 256] by cosine (ties by smaller id)."""
+        if not global_object_embeddings.is_cuda or self.n == 0:
+            raise DemoVLPHipError("shortlist_by_cosine needs a filled index and embeddings on an MI355X device")
+        with torch.no_grad():
+            ids, cos = self._global_stage(ops.rownorm_fwd(global_object_embeddings.detach().contiguous())[0], self._shortlist_size(shortlist),
+                                          int(chunk))
+        return ids.long(), cos
+
+    def _local_stage(self, local_loss, lo, om, ids):
+        lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
+        if self.fused:
+            return Fn.XattnCaptionIndexPairsFn.apply(self.local, self.capacity, self.W, self.tm, lo, om, ids, lam, gate)
+        out = torch.empty(ids.shape, device=ids.device, dtype=torch.float32)
+        for i in range(ids.shape[0]):                              # parity route: the video's captions gathered, multi-kernel grid [1, S]
+            rows = ids[i].long()
+            out[i] = local_loss.get_sim(lo[i:i + 1], self.local[rows], om[i:i + 1], None, self.tm[rows])[0]
+        return out
+
+    def _video_side(self, model, data):
+        """One block of query videos through the object tower -> (global [Nv, 256], local [Nv, G, 256], additive region mask [Nv, G])."""
+        go, lo, add_mask = model.compute_object(data["object"], data["object_mask"])
+        if lo.dtype != self.dtype:
+            raise ValueError(f"this index holds {self.dtype} embeddings, the model computes {lo.dtype}")
+        if self.fused and call("dvlp_xattn_caption_index_query_workspace_bytes", lo.shape[0], lo.shape[1], self.W) < 0:
+            raise DemoVLPHipError(f"videos of {lo.shape[1]} regions are beyond the fused kernel's range with captions of {self.W} words "
+                                  "(G <= 288 and 160 KB of LDS per pair)")
+        return go, lo.contiguous(), add_mask[:, 1:, ...].float().contiguous()
+
+    def _score(self, model, loss_fn, data, S, chunk, side=None):
+        """One block of query videos through the object tower (or its outputs ``side``) and both stages -> (qn, ids int32 [Nv, S], cos, local)."""
+        local_loss = getattr(loss_fn, "local_loss", loss_fn)
+        go, lo, om = side if side is not None else self._video_side(model, data)
+        qn = ops.rownorm_fwd(go.contiguous())[0]
+        ids, cos = self._global_stage(qn, S, chunk)
+        return qn, ids, cos, self._local_stage(local_loss, lo, om, ids)
+
+    def _ground_block(self, loss_fn, side, ids, frames):
+        """Grounding of one block's pairs (video i, index row ids[i, p]) from its object-tower outputs."""
+        local_loss = getattr(loss_fn, "local_loss", loss_fn)
+        _, lo, om = side
+        out = ops.xattn_caption_index_pairs_ground(self.local, self.capacity, self.W, self.tm, lo, om, ids.to(torch.int32).contiguous(),
+                                                   float(local_loss.lambda_softmax), local_loss.focal_type == "equal", frames)
+        inside = (ids >= 0) & (ids < self.capacity)
+        out["word_valid"] = (self.tm[ids.long().clamp(0, self.capacity - 1)] == 0) & inside[..., None]
+        if frames is not None:
+            out["word_frame"] = torch.div(out["word_region"], lo.shape[1] // int(frames), rounding_mode="floor")
+        return out
+
+    def _ground_checks(self, frames, G):
+        if not self.fused:
+            raise DemoVLPHipError("grounding needs the fused route (a bf16 index of captions with W <= 112 words, videos of G <= 288 regions): "
+                                  f"this index is {self.dtype} with W = {self.W}; there is no fp32 / long-caption grounding")
+        if frames is not None and (int(frames) < 1 or G % int(frames) != 0):
+            raise ValueError(f"frames = {frames} must be a positive divisor of G = {G}")
+
+    @staticmethod
+    def _blocks(data):
+        n = data["object"].shape[0]
+        for v0 in range(0, n, VIDEO_BLOCK):
+            yield v0, {name: t[v0:v0 + VIDEO_BLOCK] for name, t in data.items() if isinstance(t, torch.Tensor)}
+
+    def ground(self, model, loss_fn, data, ids, frames=None):
+        """Where the local similarity of (video i, index row ``ids[i, p]``) comes from; ``data`` = ``{'object', 'object_mask'}`` on the
+        device, ``ids`` int [Nv, k], typically what ``search`` returned.  -> a dict on the device (``ops.xattn_caption_index_pairs_ground``):
+        ``score`` [Nv, k] (the local addend of the search score, bit for bit), ``word_scores`` / ``word_region`` / ``word_region_weight``
+        [Nv, k, W], ``region_scores`` / ``region_word`` [Nv, k, G], ``word_valid`` bool [Nv, k, W] (words of caption ``ids[i, p]`` that are
+        not padding, from the index's stored mask) and, with ``frames`` (a divisor of G: regions are frame-major), ``frame_scores``
+        [Nv, k, frames] and ``word_frame`` = ``word_region // (G // frames)``.  Fused route only; no gradient flows."""
+        obj = data["object"]
+        self._ground_checks(frames, int(obj.shape[1] * obj.shape[2]))
+        if not (obj.is_cuda and ids.is_cuda):
+            raise DemoVLPHipError("CaptionIndex.ground runs on an MI355X device only (no CPU fallback): move the videos and ids to cuda")
+        if ids.dim() != 2 or ids.shape[0] != obj.shape[0] or ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"ids must be int [Nv = {obj.shape[0]}, k], got {ids.dtype} {tuple(ids.shape)}")
+        if self.n == 0:
+            raise ValueError("the index is empty")
+        was_training = model.training
+        model.eval()
+        res = []
+        try:
+            with torch.no_grad():
+                for v0, block in self._blocks(data):
+                    res.append(self._ground_block(loss_fn, self._video_side(model, block), ids[v0:v0 + VIDEO_BLOCK], frames))
+        finally:
+            if was_training:
+                model.train()
+        return {name: torch.cat([r[name] for r in res]) for name in res[0]}
+
+    def search(self, model, loss_fn, data, k=10, shortlist=100, chunk=65536, ground=False, frames=None):
+        """The ``k`` best captions for every video of ``data`` (``{'object', 'object_mask'}`` on the device) ->
+        ``(ids int64 [Nv, k], scores fp32 [Nv, k])`` on the device, best first, equal scores by smaller id; ids are index rows.
+        With ``ground=True``: ``(ids, scores, grounding)``, the dict of ``CaptionIndex.ground`` for the k winners (one more launch over them,
+        on the object-tower outputs the search used; ``frames`` as there).
+
+        ``loss_fn`` supplies ``lambda_softmax`` / ``focal_type`` (a ``GlobalLocalLoss`` or its ``RWALoss``).  ``shortlist``: captions per
+        video that reach the local stage, chosen by cosine (at most 1024); ``None`` or ``>= len(index)`` scores every caption (exact search).
+        ``chunk``: index rows per global-stage product.  The score is ``cos(video_i, text_j) + local(video_i, caption_j)``, the pair score of
+        ``VideoIndex.search``: an exact search here is the transpose of an exact search there.  In ``trainer.evaluate``'s terms it is
+        ``global_sims.T + local_sims``, NOT the transpose of its ``o2t_sims`` (which keeps the reference's transposed-addend quirk), so
+        metrics of search results are not comparable with the reference's evaluation numbers.  No gradient flows."""
+        k, S, chunk = self._search_checks(k, shortlist, chunk)
+        obj = data["object"]
+        if ground:
+            self._ground_checks(frames, int(obj.shape[1] * obj.shape[2]))
+        if not obj.is_cuda:
+            raise DemoVLPHipError("CaptionIndex.search runs on an MI355X device only (no CPU fallback): move the videos to cuda")
+        was_training = model.training
+        model.eval()
+        res = []
+        try:
+            with torch.no_grad():
+                for _, block in self._blocks(data):
+                    side = self._video_side(model, block)
+                    _, ids, cos, local = self._score(model, loss_fn, block, S, chunk, side)
+                    val, pos = ops.topk_rows(cos + local, k)
+                    top = torch.gather(ids, 1, pos.long()).long()
+                    res.append((top, val, self._ground_block(loss_fn, side, top, frames) if ground else None))
         finally:
             if was_training:
                 model.train()
@@ -325,3 +567,34 @@ def evaluate_t2v(model, loss_fn, batches, shortlist=None, chunk=65536):
             model.train()
     sims = two_stage_sims(np.concatenate(g), np.concatenate(ids), np.concatenate(scores))
     return dict(t2v_metrics=M.t2v_metrics(sims), sims=sims)
+
+
+def evaluate_v2t(model, loss_fn, batches, shortlist=None, chunk=65536):
+    """Video-to-text metrics of two-stage search on one loader (as ``evaluate_t2v``: caption b of a batch belongs to its video b): every
+    caption goes into one ``CaptionIndex``, every video is searched with ``shortlist``, and ``metric.v2t_metrics`` is taken of
+    ``two_stage_sims``.  Search orientation (see the module docstring): not comparable with ``trainer.evaluate``.
+    -> ``{'v2t_metrics': dict, 'sims': numpy [N captions, N videos]}`` -- text x video, the orientation ``metric.v2t_metrics`` expects (it
+    transposes to rank captions per video itself), i.e. the transpose of the [video, caption] matrix the searches produce."""
+    from . import metric as M
+    batches = list(batches)
+    ids0 = batches[0]["text"]["input_ids"]
+    N = sum(int(b["text"]["input_ids"].shape[0]) for b in batches)
+    index = CaptionIndex(N, int(ids0.shape[1]) - 1, model.compute_dtype, ids0.device).add_batches(model, batches)
+    S = index._shortlist_size(shortlist)
+    if S < N and S > TOPK_MAX:
+        raise ValueError(f"a partial shortlist is limited to {TOPK_MAX} (dvlp_topk_rows)")
+    was_training = model.training
+    model.eval()
+    g, ids, scores = [], [], []
+    try:
+        with torch.no_grad():
+            for data in batches:
+                qn, i, cos, local = index._score(model, loss_fn, data, S, int(chunk))
+                g.append(ops.gemm(qn, index.gn, qn.shape[0], N, 256, dtype=ops.F32).cpu().numpy())
+                ids.append(i.cpu().numpy())
+                scores.append((cos + local).cpu().numpy())
+    finally:
+        if was_training:
+            model.train()
+    sims = two_stage_sims(np.concatenate(g), np.concatenate(ids), np.concatenate(scores)).T
+    return dict(v2t_metrics=M.v2t_metrics(sims), sims=sims)

@@ -258,6 +258,35 @@ int dvlp_xattn_index_pairs_ground(int64_t capacity, int64_t G, const void* index
                                   float* score, float* word_scores, float* region_scores, int* word_region, float* word_region_weight,
                                   int* region_word, float* frame_scores, void* workspace, void* stream);
 
+/* Resident caption index + video-major pair list (video-to-text search, demovlp_amd/search.py): the family above with the roles swapped.
+   The index is caller-owned device memory of dvlp_xattn_caption_index_bytes(capacity, W) bytes holding, per caption of W words, what the
+   fused kernel's prep writes per call: qhat [Wp][256] and qhatT [256][Wk] in bf16 (Wp = W rounded up to 16, Wk = to 32) and the word norms
+   nq [W] in fp32, each section rounded up to 256 bytes (123 392 bytes at capacity 1, W = 99).  bf16 only, W <= 112, and a query's G inside the
+   fused range (G <= 288): anything else returns DVLP_ERR_UNSUPPORTED (size helpers: a negative value; Bi > 65535 is DVLP_ERR_SHAPE).
+     dvlp_xattn_caption_index_add        preps captions Qraw (bf16 [n][W][256]) into rows row0 .. row0 + n; a row's bytes do not depend on
+                                         the call that wrote it (several adds == one add).
+     dvlp_xattn_caption_index_pairs_fwd  preps the Bi videos Craw (bf16 [Bi][G][256]) into `workspace`
+                                         (dvlp_xattn_caption_index_query_workspace_bytes(Bi, G, W): independent of the capacity), then one
+                                         workgroup per (k, i) runs the per-pair code of the full-grid fused kernel: scores[i][k] (fp32 [Bi][K])
+                                         equals entry [i][cand[i K + k]] of dvlp_xattn_fwd's grid bit for bit.  cand is int32 [Bi][K] on the
+                                         device; an entry outside [0, capacity) reads nothing and scores NaN.  mcap is the additive word mask
+                                         of the whole index, fp32 [capacity][W]; mimg is fp32 [Bi][G].  Bi <= 65535.
+     dvlp_xattn_caption_index_pairs_ground  the same grid with the outputs of dvlp_xattn_index_pairs_ground, laid out [Bi][K][...] (score
+                                         [Bi][K], word rows [Bi][K][W], region rows [Bi][K][G], frame_scores [Bi][K][frames]); the same
+                                         argument rules (every error DVLP_ERR_SHAPE), NaN / -1 rows for a cand entry outside the index.
+                                         workspace: dvlp_xattn_caption_index_ground_workspace_bytes(Bi, G, K, W) bytes. */
+int64_t dvlp_xattn_caption_index_bytes(int64_t capacity, int64_t W);
+int dvlp_xattn_caption_index_add(int64_t capacity, int64_t W, int64_t row0, int64_t n, const void* Qraw, void* index, void* stream);
+int64_t dvlp_xattn_caption_index_query_workspace_bytes(int64_t Bi, int64_t G, int64_t W);
+int dvlp_xattn_caption_index_pairs_fwd(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G, int64_t d,
+                                       const void* Craw, const float* mimg, int64_t K, const int* cand, float lam, int gate, float* scores,
+                                       void* workspace, void* stream);
+int64_t dvlp_xattn_caption_index_ground_workspace_bytes(int64_t Bi, int64_t G, int64_t K, int64_t W);
+int dvlp_xattn_caption_index_pairs_ground(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G, int64_t d,
+                                          const void* Craw, const float* mimg, const int* cand, int64_t K, int64_t frames, float lam, int gate,
+                                          float* score, float* word_scores, float* region_scores, int* word_region, float* word_region_weight,
+                                          int* region_word, float* frame_scores, void* workspace, void* stream);
+
 /* ---- row top-k (csrc/topk.hip; no reference counterpart: the reference ranks on the host, model/metric.py) ----
    Per row m of the fp32 matrix x [M][ld] (first N columns): val[m][0..K) = the K largest values, descending, idx[m][..] = their column numbers
    + index_base (int32).  Total order: larger value first, equal values by smaller index -- np.argsort(-x, kind="stable")[:K]; -0.0 == +0.0; a NaN
