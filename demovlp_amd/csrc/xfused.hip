@@ -921,3 +921,496 @@ int dvlp_xfused_caption_index_pairs_ground(int64_t capacity, int64_t W, const vo
     hipLaunchKernelGGL(xf_caption_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bi), dim3(512), (size_t)L.total, st, a, go);
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Region-tiled pair kernel (dvlp_xattn_long_index_*): the pair score above for long videos, 1 <= G <= 1152 regions and
+// W <= 112 words, bf16.  The fused kernel keeps P1' [W][G] and P2' [G][W] resident, which is what stops it at G = 288; the score splits
+// along the region axis, so here one workgroup per pair walks the regions in tiles of 128 (one 16-row block per wave) twice, recomputing
+// S = LeakyReLU(C^ Q^T) per tile with Q^ staged once:
+//
+//   sweep 1   per tile: S, its row norms (region-local), and into per-lane accumulators the column sums of squares (-> cn[w]) and
+//             cs[w] = sum_g e, e = exp(lam (S rn + m_img - 1)) rounded to bf16.  No running maximum: z <= lam (see pair_forward).
+//   sweep 2   per tile, on the recomputed S (same code, same operands: same bits):
+//             image -> text   the gate is a per-word threshold on e; the gated, UNNORMALISED numerators go to LDS as bf16 [w][128] and
+//                             feed wc^T += C^^T_tile P1u_tile^T, accumulated in registers over all tiles (waves own 32-channel slices);
+//                             gs[w] = sum_g H e and gd[w] = sum_g H e S_pre accumulate beside it.  The per-word scale 1 / gs is applied
+//                             once at the end (to the accumulators, before they are squared).
+//             text -> image   tile-local throughout: softmax over words, gate, renormalise, P2' tile [128][w] to LDS, wc2 product,
+//                             |wc2_g|^2, cos(C_g, wc2_g) -> rc[g].
+//   end       |wc_w|^2, the word cosines, and the sum of all cosines in a fixed order.
+//
+// The cosines use <raw, ctx> = (|raw| + eps) sum P' S_pre as above.  No float atomics; every cross-wave sum is taken in wave order, so
+// the result does not depend on scheduling.  Pad rows / columns are zeros in the operands and -1e4 in the masks, as in pair_forward.
+//
+// GROUND adds the rows of dvlp_xattn_index_pairs_ground: word_region is a running "larger logit, then smaller index" key per lane and word,
+// carried across the tiles (with the gated numerator at that entry beside it); region_word / region_scores are tile-local; word_scores come
+// at the end.  word_region_weight = gated numerator (the bf16 value the kernel multiplies with) / gated sum, in fp32 -- the fused kernel
+// reports the bf16-rounded quotient instead, because that is what IT multiplies with.
+//
+// The score of the GROUND instantiation equals the other's bit for bit: floating-point contraction is switched off for everything below
+// (a fused multiply-add appears only where fmaf is written), no fast-math reassociation is in force, and GROUND touches no operand of the
+// arithmetic that ends in the score.
+// ------------------------------------------------------------------------------------------------------------------
+#pragma clang fp contract(off)
+
+constexpr int LT = 128;              // regions per tile: one 16-row block per wave
+constexpr int LPS = LT + 8;          // row stride (elements) of the P1u tile [w][128] and of the P2' tile [128][Wk <= 128]
+constexpr int LG_MAX = 1152;         // 32 frames x 36 regions
+// LDS map (bytes; fixed, whatever the shape)
+constexpr int LL_QS = 0;                                    // Q^ [Wp][FQS] bf16, staged once                       59 136
+constexpr int LL_P1 = LL_QS + 16 * FW_MAXB * FQS * 2;       // P1u tile [Wp][LPS] bf16                              30 464
+constexpr int LL_P2 = LL_P1 + 16 * FW_MAXB * LPS * 2;       // P2' tile [LT][LPS] bf16 (GROUND, at the end: weights) 34 816
+constexpr int LL_XA = LL_P2 + LT * LPS * 2;                 // four cross-wave exchanges [8][112] fp32               4 x 3 584
+constexpr int LL_XB = LL_XA + 8 * 112 * 4;                  //   (GROUND, at the end: xa + xb hold the keys [8][112] u64)
+constexpr int LL_XC = LL_XB + 8 * 112 * 4;
+constexpr int LL_XD = LL_XC + 8 * 112 * 4;
+constexpr int LL_NW2P = LL_XD + 8 * 112 * 4;                // per-wave partials of |wc2_g|^2 [8][LT] (at the end: of |wc_w|^2)  4 096
+constexpr int LL_DOTG = LL_NW2P + 8 * LT * 4;               // sum_w P2' S_pre per region [1152]                     4 608
+constexpr int LL_RC = LL_DOTG + LG_MAX * 4;                 // region cosines [1152]                                 4 608
+constexpr int LL_DOTW = LL_RC + LG_MAX * 4;                 // sum_g P1' S_pre per word [112]                          448
+constexpr int LL_GINV = LL_DOTW + 112 * 4;                  // 1 / gated sum per word [112]                            448
+constexpr int LL_RED = LL_GINV + 112 * 4;                   // the eight waves' shares of the score                     32
+constexpr int LL_TOTAL = LL_RED + 8 * 4;                    // 152 992
+static_assert(LL_TOTAL <= 160 * 1024 && LL_XA % 8 == 0 && 8 * 112 * 4 <= LT * LPS * 2 && 8 * 112 * 4 <= 8 * LT * 4, "LDS map of the tiled kernel");
+
+// S of region block rb (16 rows) against all words, with what is local to its rows
+struct TileRegs {
+    f32x4 S[FW_MAXB];      // LeakyReLU(S_pre); zeros for a block past the video and for pad words
+    float rn[4];           // 1 / (|S_row| + eps)
+    float k1[4], mi[4];    // exponent scale lam log2(e) rn and offset lam log2(e) (m_img - 1); m_img = -1e4 for pad rows
+    float mraw[4];         // m_img (0 for pad rows)
+    bool okg[4];           // a region of the video
+};
+__device__ __forceinline__ void xl_tile_s(const FusedArgs& a, const bf16* ch, const float* mimg, const bf16* Qs, int rb, float L2E, TileRegs& T) {
+    const int lane = threadIdx.x & 63, lq = lane >> 4, lc = lane & 15;
+    const int nbg = a.Gr >> 4, nwb = a.Wp >> 4;
+    const bool live = rb < nbg;                            // wave-uniform
+    bf16x8 af[8];
+    const bf16* ap = ch + (int64_t)((live ? rb : 0) * 16 + lc) * FD + 8 * lq;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) af[ks] = *(const bf16x8*)(ap + ks * 32);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int g = rb * 16 + lq * 4 + r;
+        T.okg[r] = live && g < a.G;
+        T.mraw[r] = T.okg[r] ? mimg[g] : 0.f;
+    }
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) {
+        f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (live && nb < nwb) {
+            const bf16* bp = Qs + (nb * 16 + lc) * FQS + 8 * lq;
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) c = mfma16(af[ks], *(const bf16x8*)(bp + ks * 32), c);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) c[r] = fmaxf(c[r], 0.1f * c[r]);             // LeakyReLU(0.1), loss.py:236
+        }
+        T.S[nb] = c;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float q = 0.f;
+#pragma unroll
+        for (int nb = 0; nb < FW_MAXB; ++nb) q = fmaf(T.S[nb][r], T.S[nb][r], q);
+        T.rn[r] = 1.f / (sqrtf(row16_sum(q)) + 1e-8f);
+        T.k1[r] = L2E * T.rn[r];
+        T.mi[r] = L2E * ((T.okg[r] ? T.mraw[r] : -1e4f) - 1.f);
+    }
+}
+
+template <bool GROUND>
+__device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, int i, int j, float* out, const GroundOut& go) {
+    const int tid = threadIdx.x, lane = tid & 63, lq = lane >> 4, lc = lane & 15;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nbg = a.Gr >> 4, nwb = a.Wp >> 4, nt = (nbg + 7) >> 3, nks2 = a.Wk >> 5;
+    bf16* Qs = (bf16*)(smem + LL_QS);
+    bf16* P1s = (bf16*)(smem + LL_P1);
+    bf16* P2s = (bf16*)(smem + LL_P2);
+    float *xa = (float*)(smem + LL_XA), *xb = (float*)(smem + LL_XB), *xc = (float*)(smem + LL_XC), *xd = (float*)(smem + LL_XD);
+    float *nw2p = (float*)(smem + LL_NW2P), *dotg = (float*)(smem + LL_DOTG), *rc = (float*)(smem + LL_RC);
+    float *dotw = (float*)(smem + LL_DOTW), *ginv = (float*)(smem + LL_GINV), *red = (float*)(smem + LL_RED);
+    const bf16* ch = a.chat + (int64_t)i * a.Gr * FD;
+    const bf16* ct = a.chatT + ((int64_t)i * FD + wid * 32 + lc) * a.Gk + 8 * lq;      // this wave's 32 channels of C^^T
+    const bf16* qt = a.qhatT + ((int64_t)j * FD + wid * 32 + lc) * a.Wk + 8 * lq;      // ... and of Q^^T
+    const float* mimg = a.mimg + (int64_t)i * a.G;
+    const float* mcap = a.mcap + (int64_t)j * a.W;
+    const float* nc = a.nc + (int64_t)i * a.G;
+    const float L2E = 1.4426950408889634f * a.lam;        // exp(lam x) = exp2(L2E x)
+    const float fG = (float)a.G, fW = (float)a.W;
+
+    // ---- Q^_j [Wp][256] -> LDS, kept for the whole pair; the k padding of the P2' tile (words Wp .. Wk-1) is zeroed once
+    {
+        const bf16* q = a.qhat + (int64_t)j * a.Wp * FD;
+        for (int p = tid; p < a.Wp * 32; p += blockDim.x) {
+            const int r = p >> 5, c = (p & 31) * 8;
+            *(bf16x8*)(Qs + r * FQS + c) = *(const bf16x8*)(q + r * FD + c);
+        }
+        if (a.Wk > a.Wp)
+            for (int p = tid; p < LT * (a.Wk - a.Wp); p += blockDim.x) P2s[(p / (a.Wk - a.Wp)) * LPS + a.Wp + p % (a.Wk - a.Wp)] = (bf16)0.f;
+    }
+    float mc[FW_MAXB], mcraw[FW_MAXB];       // exponent offset lam log2(e) (m_cap - 1), m_cap = -1e4 for pad columns; m_cap itself
+    bool okw[FW_MAXB];
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) {
+        const int w = nb * 16 + lc;
+        okw[nb] = nb < nwb && w < a.W;
+        mcraw[nb] = okw[nb] ? mcap[w] : 0.f;
+        mc[nb] = L2E * ((okw[nb] ? mcraw[nb] : -1e4f) - 1.f);
+    }
+    __syncthreads();
+
+    // ---- sweep 1: column sums of squares of S and cs[w] = sum_g e
+    float csq[FW_MAXB], cs[FW_MAXB];
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) { csq[nb] = 0.f; cs[nb] = 0.f; }
+    for (int t = 0; t < nt; ++t) {
+        TileRegs T;
+        xl_tile_s(a, ch, mimg, Qs, t * 8 + wid, L2E, T);
+#pragma unroll
+        for (int nb = 0; nb < FW_MAXB; ++nb) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) csq[nb] = fmaf(T.S[nb][r], T.S[nb][r], csq[nb]);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const unsigned u = pk2(__builtin_amdgcn_exp2f(fmaf(T.S[nb][2 * h], T.k1[2 * h], T.mi[2 * h])),
+                                       __builtin_amdgcn_exp2f(fmaf(T.S[nb][2 * h + 1], T.k1[2 * h + 1], T.mi[2 * h + 1])));
+                cs[nb] += pk_lo(u) + pk_hi(u);
+            }
+        }
+    }
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) { csq[nb] = col4_sum(csq[nb]); cs[nb] = col4_sum(cs[nb]); }
+    xch_put(xa, wid, lane, csq, nwb);
+    xch_put(xb, wid, lane, cs, nwb);
+    __syncthreads();
+    xch_get(xa, lane, csq, nwb);
+    xch_get(xb, lane, cs, nwb);
+    // text -> image exponent scale lam log2(e) / (|S_col| + eps); focal gate of image -> text as a per-word threshold on e (see pair_forward)
+    float cn[FW_MAXB], kc[FW_MAXB], thr[FW_MAXB], gs[FW_MAXB], gd[FW_MAXB];
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) {
+        cn[nb] = 1.f / (sqrtf(csq[nb]) + 1e-8f);
+        kc[nb] = L2E * cn[nb];
+        const float inv = cs[nb] > 0.f ? 1.f / cs[nb] : 0.f;
+        thr[nb] = a.gate ? (cs[nb] * inv) / (inv * fG) : -1.f;
+        gs[nb] = 0.f; gd[nb] = 0.f;
+    }
+
+    // ---- sweep 2
+    f32x4 acc[2][FW_MAXB];               // wc^T [d][w] times the gated sum: channels 32 wid + 16 db + 4 lq + r, word 16 nb + lc
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int nb = 0; nb < FW_MAXB; ++nb) acc[db][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    u64 kw[FW_MAXB];                     // GROUND: best image->text key of this lane's rows so far, per word, and the gated numerator there
+    float ew[FW_MAXB];
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) { kw[nb] = 0ull; ew[nb] = 0.f; }
+
+    for (int t = 0; t < nt; ++t) {
+        const int rb = t * 8 + wid, row0 = wid * 16 + lq * 4;       // this lane's four rows of the tile: row0 .. row0 + 3
+        TileRegs T;
+        xl_tile_s(a, ch, mimg, Qs, rb, L2E, T);
+        // image -> text: gated numerators of this block -> P1u tile [w][row], four consecutive regions per 8-byte write
+#pragma unroll
+        for (int nb = 0; nb < FW_MAXB; ++nb) {
+            unsigned v[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const unsigned u = pk2(__builtin_amdgcn_exp2f(fmaf(T.S[nb][2 * h], T.k1[2 * h], T.mi[2 * h])),
+                                       __builtin_amdgcn_exp2f(fmaf(T.S[nb][2 * h + 1], T.k1[2 * h + 1], T.mi[2 * h + 1])));
+                const unsigned keep = (pk_lo(u) > thr[nb] ? 0x0000ffffu : 0u) | (pk_hi(u) > thr[nb] ? 0xffff0000u : 0u);
+                v[h] = u & keep;
+                const float s0 = T.S[nb][2 * h], s1 = T.S[nb][2 * h + 1];
+                gs[nb] += pk_lo(v[h]) + pk_hi(v[h]);
+                gd[nb] = fmaf(pk_lo(v[h]), fminf(s0, 10.f * s0), fmaf(pk_hi(v[h]), fminf(s1, 10.f * s1), gd[nb]));     // S_pre: undo LeakyReLU(0.1)
+            }
+            if (nb < nwb) *(uint2*)(P1s + (nb * 16 + lc) * LPS + row0) = make_uint2(v[0], v[1]);
+            if constexpr (GROUND) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const u64 k = gr_key(gr_logit(a.lam, T.S[nb][r], T.rn[r], T.mraw[r]), rb * 16 + lq * 4 + r);       // lam (A[g][w] + m_img[g])
+                    if (T.okg[r] && k > kw[nb]) { kw[nb] = k; ew[nb] = (r & 1) ? pk_hi(v[r >> 1]) : pk_lo(v[r >> 1]); }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);            // keep the unrolled word blocks from being interleaved (register pressure)
+        }
+        // text -> image: softmax over words of lam (S cn + m_cap) per region, gate, renormalise -> P2' tile [row][w]
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float e[FW_MAXB], sum = 0.f;
+#pragma unroll
+            for (int nb = 0; nb < FW_MAXB; ++nb) {
+                e[nb] = __builtin_amdgcn_exp2f(fmaf(T.S[nb][r], kc[nb], mc[nb]));
+                sum += e[nb];
+            }
+            sum = row16_sum(sum);
+            const float inv = sum > 0.f ? 1.f / sum : 0.f;
+            const float th = a.gate ? (sum * inv) / (inv * fW) : -1.f;
+            float g1 = 0.f, g2 = 0.f;
+#pragma unroll
+            for (int nb = 0; nb < FW_MAXB; ++nb) {
+                const float sv = T.S[nb][r];
+                e[nb] = e[nb] > th ? e[nb] : 0.f;
+                g1 += e[nb]; g2 = fmaf(e[nb], fminf(sv, 10.f * sv), g2);
+            }
+            g1 = row16_sum(g1); g2 = row16_sum(g2);
+            const float is = g1 > 0.f ? 1.f / g1 : 0.f;
+#pragma unroll
+            for (int nb = 0; nb < FW_MAXB; ++nb)
+                if (nb < nwb) P2s[(row0 + r) * LPS + nb * 16 + lc] = (bf16)(e[nb] * is);
+            const int g = rb * 16 + lq * 4 + r;
+            if (rb < nbg && lc == 0) dotg[g] = g2 * is;
+            if constexpr (GROUND) {
+                u64 kg = 0ull;
+#pragma unroll
+                for (int nb = 0; nb < FW_MAXB; ++nb)
+                    if (okw[nb]) kg = gr_max(kg, gr_key(gr_logit(a.lam, T.S[nb][r], cn[nb], mcraw[nb]), nb * 16 + lc));  // lam (A2[g][w] + m_cap[w])
+                kg = gr_row16_max(kg);
+                if (T.okg[r] && lc == 0) go.region_word[g] = gr_index(kg);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();                                   // both tiles are published
+        // A operands of the two products: this tile's (at most four) 32-region steps of C^^T, and Q^^T (L2 hits after the first tile);
+        // requested after the barrier: 64 registers that the softmax passes above have no room for
+        const int k0 = t * LT;
+        const int nks1 = (a.Gk - k0) >> 5 < 4 ? (a.Gk - k0) >> 5 : 4;
+        bf16x8 ca[2][4], qa[2][4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const int k = ks < nks1 ? k0 + ks * 32 : 0;
+            ca[0][ks] = *(const bf16x8*)(ct + k); ca[1][ks] = *(const bf16x8*)(ct + (int64_t)16 * a.Gk + k);
+            const int kq = ks < nks2 ? ks * 32 : 0;
+            qa[0][ks] = *(const bf16x8*)(qt + kq); qa[1][ks] = *(const bf16x8*)(qt + (int64_t)16 * a.Wk + kq);
+        }
+        // wc^T += C^^T_tile P1u_tile^T
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            if (ks < nks1) {
+#pragma unroll
+                for (int nb = 0; nb < FW_MAXB; ++nb) {
+                    if (nb < nwb) {
+                        const bf16x8 b = *(const bf16x8*)(P1s + (nb * 16 + lc) * LPS + ks * 32 + 8 * lq);
+                        acc[0][nb] = mfma16(ca[0][ks], b, acc[0][nb]);
+                        acc[1][nb] = mfma16(ca[1][ks], b, acc[1][nb]);
+                    }
+                }
+            }
+        }
+        // |wc2_g|^2 of the tile's regions: wc2^T [d][g] = Q^^T [d][w] P2'^T, per-wave partials over this wave's 32 channels
+        for (int gb = 0; gb < 8 && t * 8 + gb < nbg; ++gb) {
+            f32x4 c0 = (f32x4){0.f, 0.f, 0.f, 0.f}, c1 = c0;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                if (ks < nks2) {
+                    const bf16x8 b = *(const bf16x8*)(P2s + (gb * 16 + lc) * LPS + ks * 32 + 8 * lq);
+                    c0 = mfma16(qa[0][ks], b, c0); c1 = mfma16(qa[1][ks], b, c1);
+                }
+            }
+            float q = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) q = fmaf(c0[r], c0[r], fmaf(c1[r], c1[r], q));
+            q = col4_sum(q);
+            if (lq == 0) nw2p[wid * LT + gb * 16 + lc] = q;
+        }
+        __syncthreads();                                   // the tiles are read; the partials are published
+        // region cosines of the tile (loss.py:320-327), the eight partials summed in wave order
+        if (tid < LT && k0 + tid < a.G) {
+            const int g = k0 + tid;
+            float q = 0.f;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) q += nw2p[w * LT + tid];
+            const float n = nc[g];
+            const float c = dotg[g] * (n + 1e-8f) / fmaxf(n * sqrtf(q), 1e-8f);
+            rc[g] = c;
+            if constexpr (GROUND) go.region_scores[g] = c;
+        }
+        // (the next tile writes P1u / P2' before its first barrier and nw2p after it; rc and dotg entries are written once)
+    }
+
+    // ---- end: gated sums over all regions, |wc_w|^2, the word cosines
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) { gs[nb] = col4_sum(gs[nb]); gd[nb] = col4_sum(gd[nb]); }
+    xch_put(xc, wid, lane, gs, nwb);
+    xch_put(xd, wid, lane, gd, nwb);
+    if constexpr (GROUND) {
+        // this wave's best key per word, and the numerator of the lane that holds it (keys of real entries are distinct)
+        u64* keys = (u64*)(smem + LL_XA);
+        float* wts = (float*)(smem + LL_P2);
+#pragma unroll
+        for (int nb = 0; nb < FW_MAXB; ++nb) {
+            const u64 k = gr_col4_max(kw[nb]);
+            if (nb < nwb) {
+                if (lq == 0) keys[wid * 112 + nb * 16 + lc] = k;
+                if (k != 0ull && kw[nb] == k) wts[wid * 112 + nb * 16 + lc] = ew[nb];
+            }
+        }
+    }
+    __syncthreads();
+    xch_get(xc, lane, gs, nwb);
+    xch_get(xd, lane, gd, nwb);
+    float* nw1p = nw2p;                  // per-wave partials of |wc_w|^2 [8][112]
+#pragma unroll
+    for (int nb = 0; nb < FW_MAXB; ++nb) {
+        const float is = gs[nb] > 0.f ? 1.f / gs[nb] : 0.f;          // P1' = H e / sum(H e): the scale the accumulators still lack
+        if (wid == 0 && lq == 0 && nb < nwb) { dotw[nb * 16 + lc] = gd[nb] * is; ginv[nb * 16 + lc] = is; }
+        float q = 0.f;
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { const float x = acc[db][nb][r] * is; q = fmaf(x, x, q); }
+        q = col4_sum(q);
+        if (nb < nwb && lq == 0) nw1p[wid * 112 + nb * 16 + lc] = q;
+    }
+    __syncthreads();
+    // ---- cosines (loss.py:286-291, 317-327): means over ALL W words / G regions (padded ones included, as the reference)
+    float part = 0.f;
+    const float* nq = a.nq + (int64_t)j * a.W;
+    for (int w = tid; w < a.W; w += blockDim.x) {
+        float q = 0.f;
+#pragma unroll
+        for (int v = 0; v < 8; ++v) q += nw1p[v * 112 + w];
+        const float n = nq[w];
+        const float c = dotw[w] * (n + 1e-8f) / fmaxf(n * sqrtf(q), 1e-8f);
+        part += c / fW;
+        if constexpr (GROUND) {
+            const u64* keys = (const u64*)(smem + LL_XA);
+            const float* wts = (const float*)(smem + LL_P2);
+            u64 k = 0ull;
+            int best = 0;
+#pragma unroll
+            for (int v = 0; v < 8; ++v) { const u64 kv = keys[v * 112 + w]; if (kv > k) { k = kv; best = v; } }
+            go.word_scores[w] = c;
+            go.word_region[w] = gr_index(k);
+            go.word_weight[w] = wts[best * 112 + w] * ginv[w];
+        }
+    }
+    for (int g = tid; g < a.G; g += blockDim.x) part += rc[g] / fG;
+    part = wave_sum(part);
+    if (lane == 0) red[wid] = part;
+    __syncthreads();
+    if (tid == 0) {
+        float t = 0.f;
+        for (int w = 0; w < 8; ++w) t += red[w];
+        *out = t;
+    }
+    if constexpr (GROUND) {
+        // frame f: mean of the region cosines over its unmasked regions, summed in region order
+        for (int f = tid; f < go.frames; f += blockDim.x) {
+            if (!go.frame_scores) break;
+            const int rf = a.G / go.frames;
+            float t = 0.f;
+            int n = 0;
+            for (int g = f * rf; g < (f + 1) * rf; ++g)
+                if (mimg[g] == 0.f) { t += rc[g]; ++n; }
+            go.frame_scores[f] = n ? t / (float)n : -__builtin_inff();
+        }
+    }
+}
+
+// resident index, query-major pair list (the grid of xf_index_pairs_kernel): workgroup (k, j) -> scores[j][k], video cand[j K + k]
+__global__ __launch_bounds__(512) void xl_index_pairs_kernel(FusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int j = blockIdx.y;
+    const int64_t o = (int64_t)j * a.K + blockIdx.x;
+    const int i = a.cand[o];
+    if (i < 0 || i >= a.Bi) {
+        if (threadIdx.x == 0) a.scores[o] = __builtin_nanf("");
+        return;
+    }
+    xl_pair_score<false>(a, smem, i, j, a.scores + o, GroundOut{});
+}
+
+// the same grid with grounding; an index outside [0, capacity) reads nothing: NaN in the float rows, -1 in the int rows
+__global__ __launch_bounds__(512) void xl_index_pairs_ground_kernel(FusedArgs a, GroundOut go) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int j = blockIdx.y;
+    const int64_t o = (int64_t)j * a.K + blockIdx.x;
+    const int i = a.cand[o];
+    go.word_scores += o * a.W; go.word_region += o * a.W; go.word_weight += o * a.W;
+    go.region_scores += o * a.G; go.region_word += o * a.G;
+    if (go.frame_scores) go.frame_scores += o * go.frames;
+    if (i < 0 || i >= a.Bi) {
+        const float nan = __builtin_nanf("");
+        if (threadIdx.x == 0) a.scores[o] = nan;
+        for (int t = threadIdx.x; t < a.W; t += blockDim.x) { go.word_scores[t] = nan; go.word_weight[t] = nan; go.word_region[t] = -1; }
+        for (int t = threadIdx.x; t < a.G; t += blockDim.x) { go.region_scores[t] = nan; go.region_word[t] = -1; }
+        if (go.frame_scores)
+            for (int t = threadIdx.x; t < go.frames; t += blockDim.x) go.frame_scores[t] = nan;
+        return;
+    }
+    xl_pair_score<true>(a, smem, i, j, a.scores + o, go);
+}
+
+// ---- C ABI of the tiled family (include/demovlp_hip.h: dvlp_xattn_long_index_*).  The resident layout, the prep kernel and the query
+//      workspace are those of dvlp_xattn_index_* (index_layout / query_layout are generic in G and W); only the range and the pair kernel differ.
+static bool xlong_ok(int64_t G, int64_t W) { return G >= 1 && G <= LG_MAX && W >= 1 && W <= 16 * FW_MAXB; }
+
+extern "C" int64_t dvlp_xattn_long_index_bytes(int64_t capacity, int64_t G) {
+    if (capacity <= 0 || capacity > INT32_MAX || G <= 0) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, 1)) return DVLP_ERR_UNSUPPORTED;
+    return index_layout(capacity, G).total;
+}
+
+extern "C" int dvlp_xattn_long_index_add(int64_t capacity, int64_t G, int64_t row0, int64_t n, const void* Craw, void* index, void* stream) {
+    dvlp_clear_status();
+    if (capacity <= 0 || capacity > INT32_MAX || G <= 0 || row0 < 0 || n <= 0 || row0 + n > capacity) return DVLP_ERR_SHAPE;
+    if (!Craw || !index) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, 1)) return DVLP_ERR_UNSUPPORTED;
+    dvlp_xfused_index_add(capacity, G, row0, n, Craw, index, (hipStream_t)stream);
+    return dvlp_launch_status();
+}
+
+extern "C" int64_t dvlp_xattn_long_index_query_workspace_bytes(int64_t Bj, int64_t W) {
+    if (Bj <= 0 || W <= 0) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(1, W)) return DVLP_ERR_UNSUPPORTED;
+    return query_layout(Bj, W).total;
+}
+
+extern "C" int dvlp_xattn_long_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                               const void* Qraw, const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores,
+                                               void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != FD || capacity <= 0 || capacity > INT32_MAX || G <= 0 || Bj <= 0 || W <= 0 || K <= 0) return DVLP_ERR_SHAPE;
+    if (Bj > 65535 || Bj * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mimg || !Qraw || !mcap || !cand || !scores || !workspace) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    FusedArgs a = xf_index_prep(capacity, G, index, mimg, Bj, W, Qraw, mcap, K, cand, lam, gate & 1, scores, workspace, (hipStream_t)stream);
+    a.stop = 0;
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xl_index_pairs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xl_index_pairs_kernel, dim3((unsigned)K, (unsigned)Bj), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream, a);
+    return dvlp_launch_status();
+}
+
+extern "C" int64_t dvlp_xattn_long_index_ground_workspace_bytes(int64_t Bj, int64_t W, int64_t K, int64_t G) {
+    if (Bj <= 0 || W <= 0 || K <= 0 || G <= 0 || Bj > 65535 || Bj * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    return query_layout(Bj, W).total;                               // the caption-side prep; every exchange lives in LDS
+}
+
+// anything wrong with the arguments, a shape beyond the range included, is DVLP_ERR_SHAPE (as dvlp_xattn_index_pairs_ground); nothing is launched then
+extern "C" int dvlp_xattn_long_index_pairs_ground(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                                  const void* Qraw, const float* mcap, const int* cand, int64_t K, int64_t frames, float lam, int gate,
+                                                  float* score, float* word_scores, float* region_scores, int* word_region,
+                                                  float* word_region_weight, int* region_word, float* frame_scores, void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != FD || capacity <= 0 || capacity > INT32_MAX || G <= 0 || Bj <= 0 || W <= 0 || K < 1) return DVLP_ERR_SHAPE;
+    if (Bj > 65535 || Bj * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mimg || !Qraw || !mcap || !cand || !score || !word_scores || !region_scores || !word_region || !word_region_weight ||
+        !region_word || !workspace)
+        return DVLP_ERR_SHAPE;
+    // frames = 0 <=> no frame_scores; otherwise frames must divide G
+    if (frames < 0 || frames > G || (frames == 0) != (frame_scores == nullptr) || (frames > 0 && G % frames != 0)) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_SHAPE;
+    FusedArgs a = xf_index_prep(capacity, G, index, mimg, Bj, W, Qraw, mcap, K, cand, lam, gate & 1, score, workspace, (hipStream_t)stream);
+    a.stop = 0;
+    GroundOut go{};
+    go.word_scores = word_scores; go.region_scores = region_scores; go.word_region = word_region; go.region_word = region_word;
+    go.word_weight = word_region_weight; go.frame_scores = frame_scores; go.frames = (int)frames;
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xl_index_pairs_ground_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xl_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bj), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream, a, go);
+    return dvlp_launch_status();
+}

@@ -686,6 +686,21 @@ class XattnIndexPairsFn(torch.autograd.Function):
         raise ops._lib.DemoVLPHipError("the index pair-list local similarity (dvlp_xattn_index_pairs_fwd) is forward only: it has no backward")
 
 
+class XattnLongIndexPairsFn(torch.autograd.Function):
+    """XattnIndexPairsFn over a long-video index (ops.xattn_long_index_add, G <= 1152; the region-tiled pair kernel).  Forward only (search);
+    a backward through it raises."""
+
+    @staticmethod
+    def forward(ctx, index, capacity, G, im_m, s, s_m, cand, lam, gate):
+        return ops.xattn_long_index_pairs_fwd(index, capacity, G, im_m.contiguous().float(), s.contiguous(), s_m.contiguous().float(),
+                                              cand.contiguous(), lam, gate)
+
+    @staticmethod
+    def backward(ctx, dscores):
+        raise ops._lib.DemoVLPHipError("the long-video pair-list local similarity (dvlp_xattn_long_index_pairs_fwd) is forward only: "
+                                       "it has no backward")
+
+
 class XattnCaptionIndexPairsFn(torch.autograd.Function):
     """xattn_score_fast of video i against the captions cand[i, k] of a resident caption index (ops.xattn_caption_index_add): [n_video, K]
     scores.  Forward only (search); a backward through it raises."""

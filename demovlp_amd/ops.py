@@ -847,6 +847,70 @@ def xattn_index_pairs_ground(index, capacity, G, m_img, Q, m_cap, cand, lam, gat
     return out
 
 
+# ---- long videos (G <= 1152): the family above on the region-tiled pair kernel (dvlp_xattn_long_index_*) ----
+def xattn_long_index_bytes(capacity, G):
+    """Bytes of the prepared (resident) video side of ``capacity`` videos with G <= 1152 regions each (the layout of ``xattn_index_bytes``)."""
+    return _size("dvlp_xattn_long_index_bytes", int(capacity), int(G))
+
+
+def xattn_long_index_add(index, capacity, G, row0, C):
+    """Prepare the videos C (bf16 [n, G, 256]) into rows row0 .. row0 + n of ``index`` (uint8 [xattn_long_index_bytes(capacity, G)])."""
+    if C.dtype != torch.bfloat16:
+        raise _lib.DemoVLPHipError(f"the resident video index is bf16 only, got {C.dtype}")
+    if C.dim() != 3 or C.shape[1] != G or C.shape[2] != 256:
+        raise _lib.DemoVLPHipError(f"expected C [n, {G}, 256], got {tuple(C.shape)}")
+    if index.numel() * index.element_size() < xattn_long_index_bytes(capacity, G):
+        raise _lib.DemoVLPHipError("index buffer smaller than dvlp_xattn_long_index_bytes(capacity, G)")
+    require_gpu(index, C)
+    call("dvlp_xattn_long_index_add", int(capacity), int(G), int(row0), C.shape[0], p(C), p(index), stream())
+
+
+def _long_pairs_checks(m_img, Q, m_cap, cand, capacity, G):
+    if Q.dtype != torch.bfloat16:
+        raise _lib.DemoVLPHipError(f"the resident video index is bf16 only, got {Q.dtype}")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != Q.shape[0]:
+        raise _lib.DemoVLPHipError(f"cand must be int32 [Bj, K], got {cand.dtype} {tuple(cand.shape)}")
+    if tuple(m_img.shape) != (capacity, G) or tuple(m_cap.shape) != tuple(Q.shape[:2]):
+        raise _lib.DemoVLPHipError(f"masks must be [capacity, G] and [Bj, W], got {tuple(m_img.shape)} and {tuple(m_cap.shape)}")
+
+
+def xattn_long_index_pairs_fwd(index, capacity, G, m_img, Q, m_cap, cand, lam, gate):
+    """``xattn_index_pairs_fwd`` for an index of ``xattn_long_index_add`` (G <= 1152, W <= 112): scores fp32 [Bj, K] of the pairs
+    (cand[j, k], j); an entry of cand outside [0, capacity) scores NaN.  Forward only."""
+    _long_pairs_checks(m_img, Q, m_cap, cand, capacity, G)
+    require_gpu(index, m_img, Q, m_cap, cand)
+    Bj, W, d = Q.shape
+    K = cand.shape[1]
+    ws = torch.empty(_size("dvlp_xattn_long_index_query_workspace_bytes", Bj, W), device=Q.device, dtype=torch.uint8)
+    scores = torch.empty((Bj, K), device=Q.device, dtype=torch.float32)
+    call("dvlp_xattn_long_index_pairs_fwd", int(capacity), int(G), p(index), p(m_img), Bj, W, d, p(Q), p(m_cap), K, p(cand), float(lam),
+         _gate_bits(gate) & 1, p(scores), p(ws), stream())
+    return scores
+
+
+def xattn_long_index_pairs_ground(index, capacity, G, m_img, Q, m_cap, cand, lam, gate, frames=None):
+    """``xattn_index_pairs_ground`` for an index of ``xattn_long_index_add``: the same dict; ``score`` is bit-equal to
+    ``xattn_long_index_pairs_fwd`` and ``word_region_weight`` is the gated numerator over the gated sum in fp32."""
+    _long_pairs_checks(m_img, Q, m_cap, cand, capacity, G)
+    if frames is not None and (int(frames) < 1 or G % int(frames) != 0):
+        raise _lib.DemoVLPHipError(f"frames = {frames} must be a positive divisor of G = {G}")
+    require_gpu(index, m_img, Q, m_cap, cand)
+    Bj, W, d = Q.shape
+    K = cand.shape[1]
+    F = 0 if frames is None else int(frames)
+    ws = torch.empty(_size("dvlp_xattn_long_index_ground_workspace_bytes", Bj, W, K, int(G)), device=Q.device, dtype=torch.uint8)
+    new = lambda n, dtype: torch.empty((Bj, K, n), device=Q.device, dtype=dtype)
+    out = dict(score=torch.empty((Bj, K), device=Q.device, dtype=torch.float32), word_scores=new(W, torch.float32),
+               region_scores=new(G, torch.float32), word_region=new(W, torch.int32), word_region_weight=new(W, torch.float32),
+               region_word=new(G, torch.int32))
+    if F:
+        out["frame_scores"] = new(F, torch.float32)
+    call("dvlp_xattn_long_index_pairs_ground", int(capacity), int(G), p(index), p(m_img), Bj, W, d, p(Q), p(m_cap), p(cand), K, F, float(lam),
+         _gate_bits(gate) & 1, p(out["score"]), p(out["word_scores"]), p(out["region_scores"]), p(out["word_region"]),
+         p(out["word_region_weight"]), p(out["region_word"]), p(out["frame_scores"]) if F else None, p(ws), stream())
+    return out
+
+
 def xattn_caption_index_bytes(capacity, W):
     """Bytes of the prepared (resident) caption side of ``capacity`` captions of W words each; raises outside the fused kernel's range."""
     return _size("dvlp_xattn_caption_index_bytes", int(capacity), int(W))

@@ -28,8 +28,15 @@ one above, ``cos(video_i, text_j) + local(video_i, caption_j)``, so an exact v2t
 ``evaluate``'s terms ``global_sims.T + local_sims``, again not the quirk matrix, and ``evaluate_v2t`` is no more comparable with the
 reference's numbers than ``evaluate_t2v``.
 
-fp32 models, and region counts beyond the fused kernel's range (G > 288), take the parity route: the raw local embeddings are kept and each
-query's shortlist is gathered and scored by the multi-kernel ``RWALoss.get_sim`` -- slow and exact, as fp32 is everywhere in this package.
+Long videos.  The fused kernel keeps both attention matrices of a pair on chip, which stops it at G = 288 regions (8 frames x 36).
+``VideoIndex(..., tiled=True)`` (bf16, G <= 1152: 32 frames x 36) keeps the same resident layout (~1.18 MB per video at G = 1152) and runs
+the local stage and the grounding on the region-tiled pair kernel (``dvlp_xattn_long_index_pairs_fwd`` / ``_pairs_ground``: two sweeps over
+128-region tiles); ``search``, ``ground``, ``search(ground=True, frames=F)`` and the state dict work as above.  Its scores
+agree with the fused kernel's to rounding (2e-3), not bit for bit.  ``CaptionIndex`` has no tiled route: long QUERY videos are out of scope.
+
+fp32 models, and region counts beyond the fused kernel's range (G > 288) without ``tiled=True``, take the parity route: the raw local
+embeddings are kept and each query's shortlist is gathered and scored by the multi-kernel ``RWALoss.get_sim`` -- slow and exact, as fp32 is
+everywhere in this package.
 """
 from __future__ import annotations
 
@@ -91,9 +98,10 @@ class _ResidentIndex:
 
 class VideoIndex(_ResidentIndex):
     """A collection of videos prepared for search.  ``capacity`` videos of ``G`` regions (frames x regions per frame) in the model's compute
-    ``dtype``; device memory is allocated at the first ``add``."""
+    ``dtype``; device memory is allocated at the first ``add``.  ``tiled=True`` (bf16, G <= 1152) selects the region-tiled pair kernel for the
+    local stage and the grounding: the route for long videos (G > 288), allowed at any G in its range."""
 
-    def __init__(self, capacity, G, dtype=torch.bfloat16, device="cuda"):
+    def __init__(self, capacity, G, dtype=torch.bfloat16, device="cuda", tiled=False):
         if int(capacity) < 1 or int(G) < 1:
             raise ValueError(f"capacity and G must be positive, got {capacity} and {G}")
         if dtype not in _DTYPES:
@@ -102,6 +110,9 @@ class VideoIndex(_ResidentIndex):
         self.n = 0
         # fused route: bf16 within the fused kernel's range (host arithmetic; a negative size is "not supported")
         self.fused = self.dtype == torch.bfloat16 and call("dvlp_xattn_index_bytes", self.capacity, self.G) > 0
+        self.tiled = bool(tiled)
+        if self.tiled and (self.dtype != torch.bfloat16 or call("dvlp_xattn_long_index_bytes", self.capacity, self.G) < 0):
+            raise ValueError(f"tiled=True needs a bfloat16 index with G <= 1152 regions, got {self.dtype} with G = {self.G}")
         self.gn = self.om = self.local = None
 
     def _alloc(self):
@@ -112,7 +123,9 @@ class VideoIndex(_ResidentIndex):
         dev = self.device
         self.gn = torch.zeros((self.capacity, 256), device=dev, dtype=torch.float32)
         self.om = torch.zeros((self.capacity, self.G), device=dev, dtype=torch.float32)
-        if self.fused:      # zeroed: the alignment gaps between its sections are never written, and the buffer is compared / saved as bytes
+        if self.tiled:      # zeroed: the alignment gaps between its sections are never written, and the buffer is compared / saved as bytes
+            self.local = torch.zeros(ops.xattn_long_index_bytes(self.capacity, self.G), device=dev, dtype=torch.uint8)
+        elif self.fused:
             self.local = torch.zeros(ops.xattn_index_bytes(self.capacity, self.G), device=dev, dtype=torch.uint8)
         else:
             self.local = torch.zeros((self.capacity, self.G, 256), device=dev, dtype=self.dtype)
@@ -138,7 +151,9 @@ class VideoIndex(_ResidentIndex):
         with torch.no_grad():
             self.gn[r0:r0 + n] = ops.rownorm_fwd(go.detach().contiguous())[0]
             self.om[r0:r0 + n] = om.detach().float()
-            if self.fused:
+            if self.tiled:
+                ops.xattn_long_index_add(self.local, self.capacity, self.G, r0, lo.detach().contiguous())
+            elif self.fused:
                 ops.xattn_index_add(self.local, self.capacity, self.G, r0, lo.detach().contiguous())
             else:
                 self.local[r0:r0 + n] = lo.detach()
@@ -162,12 +177,16 @@ class VideoIndex(_ResidentIndex):
     # ---- persistence --------------------------------------------------------------------------------------------------
     def state_dict(self):
         self._alloc()
-        return dict(capacity=self.capacity, G=self.G, dtype=str(self.dtype).replace("torch.", ""), n=self.n, fused=self.fused,
-                    gn=self.gn.cpu(), om=self.om.cpu(), local=self.local.cpu())
+        state = dict(capacity=self.capacity, G=self.G, dtype=str(self.dtype).replace("torch.", ""), n=self.n, fused=self.fused,
+                     gn=self.gn.cpu(), om=self.om.cpu(), local=self.local.cpu())
+        if self.tiled:      # (only tiled indexes write the key: every other state dict is what it was)
+            state["tiled"] = True
+        return state
 
     def load_state_dict(self, state):
-        if (state["capacity"], state["G"], _DTYPES[state["dtype"]], bool(state["fused"])) != (self.capacity, self.G, self.dtype, self.fused):
-            raise ValueError("state_dict belongs to an index of another capacity / G / dtype")
+        if (state["capacity"], state["G"], _DTYPES[state["dtype"]], bool(state["fused"]), bool(state.get("tiled", False))) != \
+                (self.capacity, self.G, self.dtype, self.fused, self.tiled):
+            raise ValueError("state_dict belongs to an index of another capacity / G / dtype / route")
         self._alloc()
         for name in ("gn", "om", "local"):
             getattr(self, name).copy_(state[name])
@@ -186,6 +205,8 @@ class VideoIndex(_ResidentIndex):
 
     def _local_stage(self, local_loss, lt, text_mask, ids):
         lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
+        if self.tiled:
+            return Fn.XattnLongIndexPairsFn.apply(self.local, self.capacity, self.G, self.om, lt, text_mask, ids, lam, gate)
         if self.fused:
             return Fn.XattnIndexPairsFn.apply(self.local, self.capacity, self.G, self.om, lt, text_mask, ids, lam, gate)
         out = torch.empty(ids.shape, device=ids.device, dtype=torch.float32)
@@ -201,7 +222,7 @@ class VideoIndex(_ResidentIndex):
         gt, lt = model.compute_text(text)
         if lt.dtype != self.dtype:
             raise ValueError(f"this index holds {self.dtype} embeddings, the model computes {lt.dtype}")
-        if self.fused and call("dvlp_xattn_index_query_workspace_bytes", lt.shape[0], lt.shape[1]) < 0:
+        if (self.fused or self.tiled) and call("dvlp_xattn_index_query_workspace_bytes", lt.shape[0], lt.shape[1]) < 0:
             raise DemoVLPHipError(f"captions of {lt.shape[1]} words are beyond the fused kernel's range (W <= 112)")
         return gt, lt.contiguous(), text_mask
 
@@ -217,17 +238,19 @@ class VideoIndex(_ResidentIndex):
         """Grounding of one block's pairs (query j, index row ids[j, p]) from its text-tower outputs."""
         local_loss = getattr(loss_fn, "local_loss", loss_fn)
         _, lt, text_mask = side
-        out = ops.xattn_index_pairs_ground(self.local, self.capacity, self.G, self.om, lt, text_mask, ids.to(torch.int32).contiguous(),
-                                           float(local_loss.lambda_softmax), local_loss.focal_type == "equal", frames)
+        ground = ops.xattn_long_index_pairs_ground if self.tiled else ops.xattn_index_pairs_ground
+        out = ground(self.local, self.capacity, self.G, self.om, lt, text_mask, ids.to(torch.int32).contiguous(),
+                     float(local_loss.lambda_softmax), local_loss.focal_type == "equal", frames)
         out["word_valid"] = att[:, 1:] > 0
         if frames is not None:
             out["word_frame"] = torch.div(out["word_region"], self.G // int(frames), rounding_mode="floor")
         return out
 
     def _ground_checks(self, frames):
-        if not self.fused:
-            raise DemoVLPHipError("grounding needs the fused route (a bf16 index with G <= 288, captions of W <= 112 words): this index is "
-                                  f"{self.dtype} with G = {self.G}; there is no fp32 / long-video grounding")
+        if not (self.fused or self.tiled):
+            raise DemoVLPHipError("grounding needs the fused route (a bf16 index with G <= 288, captions of W <= 112 words) or, for long videos, "
+                                  f"a bf16 index built with tiled=True (G <= 1152): this index is {self.dtype} with G = {self.G}; there is no "
+                                  "fp32 grounding")
         if frames is not None and (int(frames) < 1 or self.G % int(frames) != 0):
             raise ValueError(f"frames = {frames} must be a positive divisor of G = {self.G}")
 
@@ -538,17 +561,18 @@ def two_stage_sims(global_sims, ids, scores):
     return sims
 
 
-def evaluate_t2v(model, loss_fn, batches, shortlist=None, chunk=65536):
+def evaluate_t2v(model, loss_fn, batches, shortlist=None, chunk=65536, tiled=False):
     """Text-to-video metrics of two-stage search on one loader (a re-iterable of tokenised batches ``{'text', 'object', 'object_mask'}``, query
     b of a batch belonging to its video b): every video goes into one ``VideoIndex``, every caption is searched with ``shortlist``, and
     ``metric.t2v_metrics`` is taken of ``two_stage_sims``.  Comparing ``shortlist=None`` with a partial one measures what the shortlist
-    costs in recall.  Search orientation (see the module docstring): not comparable with ``trainer.evaluate``.
+    costs in recall.  ``tiled``: passed on to ``VideoIndex`` (long videos).  Search orientation (see the module docstring): not comparable
+    with ``trainer.evaluate``.
     -> ``{'t2v_metrics': dict, 'sims': numpy [N, N]}``."""
     from . import metric as M
     batches = list(batches)
     N = sum(int(b["object"].shape[0]) for b in batches)
     obj = batches[0]["object"]
-    index = VideoIndex(N, int(obj.shape[1] * obj.shape[2]), model.compute_dtype, obj.device).add_batches(model, batches)
+    index = VideoIndex(N, int(obj.shape[1] * obj.shape[2]), model.compute_dtype, obj.device, tiled=tiled).add_batches(model, batches)
     S = index._shortlist_size(shortlist)
     if S < N and S > TOPK_MAX:
         raise ValueError(f"a partial shortlist is limited to {TOPK_MAX} (dvlp_topk_rows)")

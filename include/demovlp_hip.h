@@ -258,6 +258,30 @@ int dvlp_xattn_index_pairs_ground(int64_t capacity, int64_t G, const void* index
                                   float* score, float* word_scores, float* region_scores, int* word_region, float* word_region_weight,
                                   int* region_word, float* frame_scores, void* workspace, void* stream);
 
+/* Long videos (no reference counterpart): the resident video index, pair list and grounding above for 1 <= G <= 1152 regions (32 frames x 36)
+   and W <= 112 words, bf16, on a region-tiled pair kernel (csrc/xfused.hip): one workgroup per pair walks the regions twice in
+   tiles of 128 with O(tile) LDS, instead of keeping both attention matrices resident.  The index layout, the query workspace, the argument
+   lists, the outputs and the error rules are those of dvlp_xattn_index_* (a row of the index at G <= 288 has the same bytes in both
+   families; ~1.18 MB per video at G = 1152); only the range differs -- the size helpers return a negative DVLP_ERR_* outside it, the calls
+   DVLP_ERR_UNSUPPORTED (pairs_ground: DVLP_ERR_SHAPE, as its sibling).  A cand entry outside [0, capacity) reads nothing: NaN scores, -1
+   indices.  Scores agree with dvlp_xattn_index_pairs_fwd to rounding (2e-3), not bit for bit: the softmax numerators are summed per tile
+   and the image->text context is scaled after its product.  dvlp_xattn_long_index_pairs_ground's score equals
+   dvlp_xattn_long_index_pairs_fwd's bit for bit, and
+     word_region_weight = gated softmax numerator at word_region[w] (the bf16 value the kernel multiplies with) / gated sum over all regions,
+                          in fp32 -- this kernel multiplies by UNNORMALISED numerators, so there is no bf16 quotient to report.
+   No float atomics; results do not depend on scheduling. */
+int64_t dvlp_xattn_long_index_bytes(int64_t capacity, int64_t G);
+int dvlp_xattn_long_index_add(int64_t capacity, int64_t G, int64_t row0, int64_t n, const void* Craw, void* index, void* stream);
+int64_t dvlp_xattn_long_index_query_workspace_bytes(int64_t Bj, int64_t W);
+int dvlp_xattn_long_index_pairs_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                    const void* Qraw, const float* mcap, int64_t K, const int* cand, float lam, int gate, float* scores,
+                                    void* workspace, void* stream);
+int64_t dvlp_xattn_long_index_ground_workspace_bytes(int64_t Bj, int64_t W, int64_t K, int64_t G);
+int dvlp_xattn_long_index_pairs_ground(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                       const void* Qraw, const float* mcap, const int* cand, int64_t K, int64_t frames, float lam, int gate,
+                                       float* score, float* word_scores, float* region_scores, int* word_region, float* word_region_weight,
+                                       int* region_word, float* frame_scores, void* workspace, void* stream);
+
 /* Resident caption index + video-major pair list (video-to-text search, demovlp_amd/search.py): the family above with the roles swapped.
    The index is caller-owned device memory of dvlp_xattn_caption_index_bytes(capacity, W) bytes holding, per caption of W words, what the
    fused kernel's prep writes per call: qhat [Wp][256] and qhatT [256][Wk] in bf16 (Wp = W rounded up to 16, Wk = to 32) and the word norms
