@@ -1343,6 +1343,43 @@ __global__ __launch_bounds__(512) void xl_index_pairs_ground_kernel(FusedArgs a,
     xl_pair_score<true>(a, smem, i, j, a.scores + o, go);
 }
 
+// resident CAPTION index, video-major pair list (the grid and hole rule of xf_caption_index_pairs_kernel, the body of xl_index_pairs_kernel):
+// workgroup (k, i) -> scores[i][k], caption cand[i K + k] of the index (a.Bj = its capacity), video i of the per-call workspace.  k is the
+// fast grid axis, so the workgroups in flight together share video i (1.18 MB at G = 1152) in L2 and stream one caption each.
+__global__ __launch_bounds__(512) void xl_caption_index_pairs_kernel(FusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int i = blockIdx.y;
+    const int64_t o = (int64_t)i * a.K + blockIdx.x;
+    const int j = a.cand[o];
+    if (j < 0 || j >= a.Bj) {
+        if (threadIdx.x == 0) a.scores[o] = __builtin_nanf("");
+        return;
+    }
+    xl_pair_score<false>(a, smem, i, j, a.scores + o, GroundOut{});
+}
+
+// the same grid with grounding: rows laid out [Bi][K][...]; an index outside [0, capacity) reads nothing: NaN in the float rows, -1 in the
+// int rows
+__global__ __launch_bounds__(512) void xl_caption_index_pairs_ground_kernel(FusedArgs a, GroundOut go) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int i = blockIdx.y;
+    const int64_t o = (int64_t)i * a.K + blockIdx.x;
+    const int j = a.cand[o];
+    go.word_scores += o * a.W; go.word_region += o * a.W; go.word_weight += o * a.W;
+    go.region_scores += o * a.G; go.region_word += o * a.G;
+    if (go.frame_scores) go.frame_scores += o * go.frames;
+    if (j < 0 || j >= a.Bj) {
+        const float nan = __builtin_nanf("");
+        if (threadIdx.x == 0) a.scores[o] = nan;
+        for (int t = threadIdx.x; t < a.W; t += blockDim.x) { go.word_scores[t] = nan; go.word_weight[t] = nan; go.word_region[t] = -1; }
+        for (int t = threadIdx.x; t < a.G; t += blockDim.x) { go.region_scores[t] = nan; go.region_word[t] = -1; }
+        if (go.frame_scores)
+            for (int t = threadIdx.x; t < go.frames; t += blockDim.x) go.frame_scores[t] = nan;
+        return;
+    }
+    xl_pair_score<true>(a, smem, i, j, a.scores + o, go);
+}
+
 // ---- C ABI of the tiled family (include/demovlp_hip.h: dvlp_xattn_long_index_*).  The resident layout, the prep kernel and the query
 //      workspace are those of dvlp_xattn_index_* (index_layout / query_layout are generic in G and W); only the range and the pair kernel differ.
 static bool xlong_ok(int64_t G, int64_t W) { return G >= 1 && G <= LG_MAX && W >= 1 && W <= 16 * FW_MAXB; }
@@ -1412,5 +1449,64 @@ extern "C" int dvlp_xattn_long_index_pairs_ground(int64_t capacity, int64_t G, c
     { static bool once = false; if (!once) { once = true;
         (void)hipFuncSetAttribute((const void*)xl_index_pairs_ground_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
     hipLaunchKernelGGL(xl_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bj), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream, a, go);
+    return dvlp_launch_status();
+}
+
+// ---- C ABI of the video-major tiled family (dvlp_xattn_long_caption_index_*): the resident caption side is the one
+//      dvlp_xattn_caption_index_bytes / _add define (query_layout is generic in W, and W <= 112 in both families), the video-side prep and
+//      workspace are those of dvlp_xattn_caption_index_* (index_layout at capacity Bi); only the range of G and the pair kernel differ.
+extern "C" int64_t dvlp_xattn_long_caption_index_query_workspace_bytes(int64_t Bi, int64_t G, int64_t W) {
+    if (Bi <= 0 || G <= 0 || W <= 0 || Bi > 65535) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    return index_layout(Bi, G).total;
+}
+
+extern "C" int dvlp_xattn_long_caption_index_pairs_fwd(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G,
+                                                       int64_t d, const void* Craw, const float* mimg, int64_t K, const int* cand, float lam,
+                                                       int gate, float* scores, void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != FD || capacity <= 0 || capacity > INT32_MAX || W <= 0 || Bi <= 0 || G <= 0 || K <= 0) return DVLP_ERR_SHAPE;
+    if (Bi > 65535 || Bi * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mcap || !Craw || !mimg || !cand || !scores || !workspace) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    FusedArgs a = xf_caption_index_prep(capacity, W, index, mcap, Bi, G, Craw, mimg, K, cand, lam, gate & 1, scores, workspace, (hipStream_t)stream);
+    a.stop = 0;
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xl_caption_index_pairs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xl_caption_index_pairs_kernel, dim3((unsigned)K, (unsigned)Bi), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream, a);
+    return dvlp_launch_status();
+}
+
+extern "C" int64_t dvlp_xattn_long_caption_index_ground_workspace_bytes(int64_t Bi, int64_t G, int64_t K, int64_t W) {
+    if (Bi <= 0 || G <= 0 || K <= 0 || W <= 0 || Bi > 65535 || Bi * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    return index_layout(Bi, G).total;                               // the video-side prep; every exchange lives in LDS
+}
+
+// anything wrong with the arguments, a shape beyond the range included, is DVLP_ERR_SHAPE (as dvlp_xattn_long_index_pairs_ground); nothing is
+// launched then
+extern "C" int dvlp_xattn_long_caption_index_pairs_ground(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G,
+                                                          int64_t d, const void* Craw, const float* mimg, const int* cand, int64_t K,
+                                                          int64_t frames, float lam, int gate, float* score, float* word_scores,
+                                                          float* region_scores, int* word_region, float* word_region_weight, int* region_word,
+                                                          float* frame_scores, void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != FD || capacity <= 0 || capacity > INT32_MAX || W <= 0 || Bi <= 0 || G <= 0 || K < 1) return DVLP_ERR_SHAPE;
+    if (Bi > 65535 || Bi * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mcap || !Craw || !mimg || !cand || !score || !word_scores || !region_scores || !word_region || !word_region_weight ||
+        !region_word || !workspace)
+        return DVLP_ERR_SHAPE;
+    // frames = 0 <=> no frame_scores; otherwise frames must divide G
+    if (frames < 0 || frames > G || (frames == 0) != (frame_scores == nullptr) || (frames > 0 && G % frames != 0)) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_SHAPE;
+    FusedArgs a = xf_caption_index_prep(capacity, W, index, mcap, Bi, G, Craw, mimg, K, cand, lam, gate & 1, score, workspace, (hipStream_t)stream);
+    a.stop = 0;
+    GroundOut go{};
+    go.word_scores = word_scores; go.region_scores = region_scores; go.word_region = word_region; go.region_word = region_word;
+    go.word_weight = word_region_weight; go.frame_scores = frame_scores; go.frames = (int)frames;
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xl_caption_index_pairs_ground_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xl_caption_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bi), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream, a,
+                       go);
     return dvlp_launch_status();
 }

@@ -716,6 +716,21 @@ class XattnCaptionIndexPairsFn(torch.autograd.Function):
                                        "it has no backward")
 
 
+class XattnLongCaptionIndexPairsFn(torch.autograd.Function):
+    """XattnCaptionIndexPairsFn for long query videos (G <= 1152; the region-tiled pair kernel on the video-major grid).  Forward only
+    (search); a backward through it raises."""
+
+    @staticmethod
+    def forward(ctx, index, capacity, W, s_m, im, im_m, cand, lam, gate):
+        return ops.xattn_long_caption_index_pairs_fwd(index, capacity, W, s_m.contiguous().float(), im.contiguous(), im_m.contiguous().float(),
+                                                      cand.contiguous(), lam, gate)
+
+    @staticmethod
+    def backward(ctx, dscores):
+        raise ops._lib.DemoVLPHipError("the long-video caption-index pair-list local similarity (dvlp_xattn_long_caption_index_pairs_fwd) is "
+                                       "forward only: it has no backward")
+
+
 class RWATailFn(torch.autograd.Function):
     """model/loss.py:105-116 on a given score matrix."""
 

@@ -989,6 +989,45 @@ def xattn_caption_index_pairs_ground(index, capacity, W, m_cap, C, m_img, cand, 
     return out
 
 
+# ---- long QUERY videos (G <= 1152) over the same resident caption index: the region-tiled pair kernel on the video-major grid
+#      (dvlp_xattn_long_caption_index_*) ----
+def xattn_long_caption_index_pairs_fwd(index, capacity, W, m_cap, C, m_img, cand, lam, gate):
+    """``xattn_caption_index_pairs_fwd`` for videos of G <= 1152 regions (same index, same arguments): scores fp32 [Bi, K] of the pairs
+    (i, cand[i, k]), bit-equal to ``xattn_long_index_pairs_fwd`` on the same pairs; an entry of cand outside [0, capacity) scores NaN.
+    Forward only."""
+    _caption_index_checks(index, capacity, W, m_cap, C, m_img, cand)
+    Bi, G, d = C.shape
+    K = cand.shape[1]
+    ws = torch.empty(_size("dvlp_xattn_long_caption_index_query_workspace_bytes", Bi, G, int(W)), device=C.device, dtype=torch.uint8)
+    scores = torch.empty((Bi, K), device=C.device, dtype=torch.float32)
+    call("dvlp_xattn_long_caption_index_pairs_fwd", int(capacity), int(W), p(index), p(m_cap), Bi, G, d, p(C), p(m_img), K, p(cand), float(lam),
+         _gate_bits(gate) & 1, p(scores), p(ws), stream())
+    return scores
+
+
+def xattn_long_caption_index_pairs_ground(index, capacity, W, m_cap, C, m_img, cand, lam, gate, frames=None):
+    """``xattn_caption_index_pairs_ground`` for videos of G <= 1152 regions: the same dict; ``score`` is bit-equal to
+    ``xattn_long_caption_index_pairs_fwd`` and ``word_region_weight`` is the gated numerator over the gated sum in fp32, as in
+    ``xattn_long_index_pairs_ground``."""
+    if frames is not None and (C.dim() != 3 or int(frames) < 1 or C.shape[1] % int(frames) != 0):
+        raise _lib.DemoVLPHipError(f"frames = {frames} must be a positive divisor of G = {C.shape[1] if C.dim() == 3 else None}")
+    _caption_index_checks(index, capacity, W, m_cap, C, m_img, cand)
+    Bi, G, d = C.shape
+    K = cand.shape[1]
+    F = 0 if frames is None else int(frames)
+    ws = torch.empty(_size("dvlp_xattn_long_caption_index_ground_workspace_bytes", Bi, G, K, int(W)), device=C.device, dtype=torch.uint8)
+    new = lambda n, dtype: torch.empty((Bi, K, n), device=C.device, dtype=dtype)
+    out = dict(score=torch.empty((Bi, K), device=C.device, dtype=torch.float32), word_scores=new(W, torch.float32),
+               region_scores=new(G, torch.float32), word_region=new(W, torch.int32), word_region_weight=new(W, torch.float32),
+               region_word=new(G, torch.int32))
+    if F:
+        out["frame_scores"] = new(F, torch.float32)
+    call("dvlp_xattn_long_caption_index_pairs_ground", int(capacity), int(W), p(index), p(m_cap), Bi, G, d, p(C), p(m_img), p(cand), K, F,
+         float(lam), _gate_bits(gate) & 1, p(out["score"]), p(out["word_scores"]), p(out["region_scores"]), p(out["word_region"]),
+         p(out["word_region_weight"]), p(out["region_word"]), p(out["frame_scores"]) if F else None, p(ws), stream())
+    return out
+
+
 def topk_rows(x, K, N=None, index_base=0, out=None, merge=False):
     """x fp32 [M, ld] (first N columns; default all) -> (val fp32 [M, K], idx int32 [M, K]): per row the K largest values in descending order,
     ties by smaller index (np.argsort(-x, kind="stable")[:, :K] + index_base), NaN last, (-inf, -1) where N < K.  ``out`` = (val, idx) to write

@@ -32,7 +32,10 @@ Long videos.  The fused kernel keeps both attention matrices of a pair on chip, 
 ``VideoIndex(..., tiled=True)`` (bf16, G <= 1152: 32 frames x 36) keeps the same resident layout (~1.18 MB per video at G = 1152) and runs
 the local stage and the grounding on the region-tiled pair kernel (``dvlp_xattn_long_index_pairs_fwd`` / ``_pairs_ground``: two sweeps over
 128-region tiles); ``search``, ``ground``, ``search(ground=True, frames=F)`` and the state dict work as above.  Its scores
-agree with the fused kernel's to rounding (2e-3), not bit for bit.  ``CaptionIndex`` has no tiled route: long QUERY videos are out of scope.
+agree with the fused kernel's to rounding (2e-3), not bit for bit.  ``CaptionIndex(..., tiled=True)`` (bf16, W <= 112) is the same route for
+long QUERY videos: the resident caption side is byte for byte that of a fused index, and the local stage and the grounding run the tiled
+pair kernel on the video-major grid (``dvlp_xattn_long_caption_index_pairs_fwd`` / ``_pairs_ground``), bit-equal per pair to
+``VideoIndex(..., tiled=True)``.
 
 fp32 models, and region counts beyond the fused kernel's range (G > 288) without ``tiled=True``, take the parity route: the raw local
 embeddings are kept and each query's shortlist is gathered and scored by the multi-kernel ``RWALoss.get_sim`` -- slow and exact, as fp32 is
@@ -326,9 +329,11 @@ class CaptionIndex(_ResidentIndex):
     Resident: the normalised global text embeddings ``gn`` [capacity, 256], the additive word masks ``tm`` [capacity, W] and the caption side
     of the fused local-similarity kernel exactly as that kernel reads it (``dvlp_xattn_caption_index_add``: 123 392 bytes per caption at
     W = 99).  bf16 with W <= 112 is the ``fused`` route; anything else keeps the raw embeddings [capacity, W, 256] and scores each query
-    video's shortlist with ``RWALoss.get_sim`` on a [1, S] grid (the parity route: exact and slow)."""
+    video's shortlist with ``RWALoss.get_sim`` on a [1, S] grid (the parity route: exact and slow).  ``tiled=True`` (bf16, W <= 112) keeps
+    the same resident bytes and selects the region-tiled pair kernel for the local stage and the grounding: the route for long query
+    videos (288 < G <= 1152), allowed at any G in its range."""
 
-    def __init__(self, capacity, W, dtype=torch.bfloat16, device="cuda"):
+    def __init__(self, capacity, W, dtype=torch.bfloat16, device="cuda", tiled=False):
         if int(capacity) < 1 or int(W) < 1:
             raise ValueError(f"capacity and W must be positive, got {capacity} and {W}")
         if dtype not in _DTYPES:
@@ -337,6 +342,9 @@ class CaptionIndex(_ResidentIndex):
         self.n = 0
         # fused route: bf16 within the fused kernel's range (host arithmetic; a negative size is "not supported")
         self.fused = self.dtype == torch.bfloat16 and call("dvlp_xattn_caption_index_bytes", self.capacity, self.W) > 0
+        self.tiled = bool(tiled)
+        if self.tiled and not self.fused:      # (one resident layout: a tiled index is a fused index with another pair kernel)
+            raise ValueError(f"tiled=True needs a bfloat16 index of captions with W <= 112 words, got {self.dtype} with W = {self.W}")
         self.gn = self.tm = self.local = None
 
     def _alloc(self):
@@ -401,12 +409,17 @@ class CaptionIndex(_ResidentIndex):
     # ---- persistence --------------------------------------------------------------------------------------------------
     def state_dict(self):
         self._alloc()
-        return dict(capacity=self.capacity, W=self.W, dtype=str(self.dtype).replace("torch.", ""), n=self.n, fused=self.fused,
-                    gn=self.gn.cpu(), tm=self.tm.cpu(), local=self.local.cpu())
+        state = dict(capacity=self.capacity, W=self.W, dtype=str(self.dtype).replace("torch.", ""), n=self.n, fused=self.fused,
+                     gn=self.gn.cpu(), tm=self.tm.cpu(), local=self.local.cpu())
+        if self.tiled:      # (only tiled indexes write the key: every other state dict is what it was)
+            state["tiled"] = True
+        return state
 
     def load_state_dict(self, state):
         if (state["capacity"], state["W"], _DTYPES[state["dtype"]], bool(state["fused"])) != (self.capacity, self.W, self.dtype, self.fused):
             raise ValueError("state_dict belongs to an index of another capacity / W / dtype")
+        if bool(state.get("tiled", False)) != self.tiled:
+            raise ValueError("state_dict belongs to an index of another route (tiled / not tiled)")
         self._alloc()
         for name in ("gn", "tm", "local"):
             getattr(self, name).copy_(state[name])
@@ -426,6 +439,8 @@ class CaptionIndex(_ResidentIndex):
 
     def _local_stage(self, local_loss, lo, om, ids):
         lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
+        if self.tiled:
+            return Fn.XattnLongCaptionIndexPairsFn.apply(self.local, self.capacity, self.W, self.tm, lo, om, ids, lam, gate)
         if self.fused:
             return Fn.XattnCaptionIndexPairsFn.apply(self.local, self.capacity, self.W, self.tm, lo, om, ids, lam, gate)
         out = torch.empty(ids.shape, device=ids.device, dtype=torch.float32)
@@ -439,7 +454,10 @@ class CaptionIndex(_ResidentIndex):
         go, lo, add_mask = model.compute_object(data["object"], data["object_mask"])
         if lo.dtype != self.dtype:
             raise ValueError(f"this index holds {self.dtype} embeddings, the model computes {lo.dtype}")
-        if self.fused and call("dvlp_xattn_caption_index_query_workspace_bytes", lo.shape[0], lo.shape[1], self.W) < 0:
+        if self.tiled:
+            if call("dvlp_xattn_long_caption_index_query_workspace_bytes", lo.shape[0], lo.shape[1], self.W) < 0:
+                raise DemoVLPHipError(f"videos of {lo.shape[1]} regions are beyond the tiled kernel's range (G <= 1152)")
+        elif self.fused and call("dvlp_xattn_caption_index_query_workspace_bytes", lo.shape[0], lo.shape[1], self.W) < 0:
             raise DemoVLPHipError(f"videos of {lo.shape[1]} regions are beyond the fused kernel's range with captions of {self.W} words "
                                   "(G <= 288 and 160 KB of LDS per pair)")
         return go, lo.contiguous(), add_mask[:, 1:, ...].float().contiguous()
@@ -456,8 +474,9 @@ class CaptionIndex(_ResidentIndex):
         """Grounding of one block's pairs (video i, index row ids[i, p]) from its object-tower outputs."""
         local_loss = getattr(loss_fn, "local_loss", loss_fn)
         _, lo, om = side
-        out = ops.xattn_caption_index_pairs_ground(self.local, self.capacity, self.W, self.tm, lo, om, ids.to(torch.int32).contiguous(),
-                                                   float(local_loss.lambda_softmax), local_loss.focal_type == "equal", frames)
+        ground = ops.xattn_long_caption_index_pairs_ground if self.tiled else ops.xattn_caption_index_pairs_ground
+        out = ground(self.local, self.capacity, self.W, self.tm, lo, om, ids.to(torch.int32).contiguous(),
+                     float(local_loss.lambda_softmax), local_loss.focal_type == "equal", frames)
         inside = (ids >= 0) & (ids < self.capacity)
         out["word_valid"] = (self.tm[ids.long().clamp(0, self.capacity - 1)] == 0) & inside[..., None]
         if frames is not None:
@@ -483,7 +502,7 @@ class CaptionIndex(_ResidentIndex):
         ``score`` [Nv, k] (the local addend of the search score, bit for bit), ``word_scores`` / ``word_region`` / ``word_region_weight``
         [Nv, k, W], ``region_scores`` / ``region_word`` [Nv, k, G], ``word_valid`` bool [Nv, k, W] (words of caption ``ids[i, p]`` that are
         not padding, from the index's stored mask) and, with ``frames`` (a divisor of G: regions are frame-major), ``frame_scores``
-        [Nv, k, frames] and ``word_frame`` = ``word_region // (G // frames)``.  Fused route only; no gradient flows."""
+        [Nv, k, frames] and ``word_frame`` = ``word_region // (G // frames)``.  Fused and tiled routes only; no gradient flows."""
         obj = data["object"]
         self._ground_checks(frames, int(obj.shape[1] * obj.shape[2]))
         if not (obj.is_cuda and ids.is_cuda):
@@ -593,17 +612,18 @@ def evaluate_t2v(model, loss_fn, batches, shortlist=None, chunk=65536, tiled=Fal
     return dict(t2v_metrics=M.t2v_metrics(sims), sims=sims)
 
 
-def evaluate_v2t(model, loss_fn, batches, shortlist=None, chunk=65536):
+def evaluate_v2t(model, loss_fn, batches, shortlist=None, chunk=65536, tiled=False):
     """Video-to-text metrics of two-stage search on one loader (as ``evaluate_t2v``: caption b of a batch belongs to its video b): every
     caption goes into one ``CaptionIndex``, every video is searched with ``shortlist``, and ``metric.v2t_metrics`` is taken of
-    ``two_stage_sims``.  Search orientation (see the module docstring): not comparable with ``trainer.evaluate``.
+    ``two_stage_sims``.  ``tiled``: passed on to ``CaptionIndex`` (long videos).  Search orientation (see the module docstring): not
+    comparable with ``trainer.evaluate``.
     -> ``{'v2t_metrics': dict, 'sims': numpy [N captions, N videos]}`` -- text x video, the orientation ``metric.v2t_metrics`` expects (it
     transposes to rank captions per video itself), i.e. the transpose of the [video, caption] matrix the searches produce."""
     from . import metric as M
     batches = list(batches)
     ids0 = batches[0]["text"]["input_ids"]
     N = sum(int(b["text"]["input_ids"].shape[0]) for b in batches)
-    index = CaptionIndex(N, int(ids0.shape[1]) - 1, model.compute_dtype, ids0.device).add_batches(model, batches)
+    index = CaptionIndex(N, int(ids0.shape[1]) - 1, model.compute_dtype, ids0.device, tiled=tiled).add_batches(model, batches)
     S = index._shortlist_size(shortlist)
     if S < N and S > TOPK_MAX:
         raise ValueError(f"a partial shortlist is limited to {TOPK_MAX} (dvlp_topk_rows)")

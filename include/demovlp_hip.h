@@ -311,6 +311,26 @@ int dvlp_xattn_caption_index_pairs_ground(int64_t capacity, int64_t W, const voi
                                           float* score, float* word_scores, float* region_scores, int* word_region, float* word_region_weight,
                                           int* region_word, float* frame_scores, void* workspace, void* stream);
 
+/* Long QUERY videos over the resident caption index (no reference counterpart): dvlp_xattn_caption_index_pairs_fwd / _pairs_ground
+   for 1 <= G <= 1152 regions, W <= 112 words, bf16, on the region-tiled pair kernel of dvlp_xattn_long_index_* with the video-major (K, Bi)
+   grid.  The resident side is the index dvlp_xattn_caption_index_bytes / _add define, byte for byte: there is no add or bytes entry of this
+   family.  The argument lists, the [Bi][K][...] outputs, the NaN / -1 rows of a cand entry outside [0, capacity) and the argument rules are
+   those of dvlp_xattn_caption_index_*; only the range of G differs -- the size helpers return a negative DVLP_ERR_* outside it, _pairs_fwd
+   DVLP_ERR_UNSUPPORTED, _pairs_ground DVLP_ERR_SHAPE.  workspace (the video-side prep): _query_workspace_bytes(Bi, G, W) resp.
+   _ground_workspace_bytes(Bi, G, K, W) bytes, at G <= 288 the sizes of the short family.  scores[i][k] equals, bit for bit, what
+   dvlp_xattn_long_index_pairs_fwd gives for the pair (video i, caption cand[i K + k]) from a video index of the same videos, every grounding
+   row likewise, and _pairs_ground's score equals _pairs_fwd's: the per-pair code is shared and a prepared row's bytes do not depend on the
+   call that wrote it.  word_region_weight is the fp32 quotient of dvlp_xattn_long_index_pairs_ground.  No float atomics. */
+int64_t dvlp_xattn_long_caption_index_query_workspace_bytes(int64_t Bi, int64_t G, int64_t W);
+int dvlp_xattn_long_caption_index_pairs_fwd(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G, int64_t d,
+                                            const void* Craw, const float* mimg, int64_t K, const int* cand, float lam, int gate, float* scores,
+                                            void* workspace, void* stream);
+int64_t dvlp_xattn_long_caption_index_ground_workspace_bytes(int64_t Bi, int64_t G, int64_t K, int64_t W);
+int dvlp_xattn_long_caption_index_pairs_ground(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G, int64_t d,
+                                               const void* Craw, const float* mimg, const int* cand, int64_t K, int64_t frames, float lam,
+                                               int gate, float* score, float* word_scores, float* region_scores, int* word_region,
+                                               float* word_region_weight, int* region_word, float* frame_scores, void* workspace, void* stream);
+
 /* ---- row top-k (csrc/topk.hip; no reference counterpart: the reference ranks on the host, model/metric.py) ----
    Per row m of the fp32 matrix x [M][ld] (first N columns): val[m][0..K) = the K largest values, descending, idx[m][..] = their column numbers
    + index_base (int32).  Total order: larger value first, equal values by smaller index -- np.argsort(-x, kind="stable")[:K]; -0.0 == +0.0; a NaN
