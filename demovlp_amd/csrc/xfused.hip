@@ -981,10 +981,15 @@ struct TileRegs {
     float mraw[4];         // m_img (0 for pad rows)
     bool okg[4];           // a region of the video
 };
-__device__ __forceinline__ void xl_tile_s(const FusedArgs& a, const bf16* ch, const float* mimg, const bf16* Qs, int rb, float L2E, TileRegs& T) {
+// RANGE (moments): the video side is the regions [g0, g1) only.  Blocks are still the video's own (absolute) 16-row blocks, so every
+// operand keeps its alignment; a row outside the range is a neighbouring frame's, not zeros, and its S is forced to zero here -- from there
+// on it behaves like a pad row (e = 0, nothing in the column sums, zeros in the P1u tile).
+template <bool RANGE>
+__device__ __forceinline__ void xl_tile_s(const FusedArgs& a, const bf16* ch, const float* mimg, const bf16* Qs, int rb, int g0, int g1, float L2E,
+                                          TileRegs& T) {
     const int lane = threadIdx.x & 63, lq = lane >> 4, lc = lane & 15;
     const int nbg = a.Gr >> 4, nwb = a.Wp >> 4;
-    const bool live = rb < nbg;                            // wave-uniform
+    const bool live = RANGE ? rb * 16 < g1 && rb * 16 + 16 > g0 : rb < nbg;      // wave-uniform
     bf16x8 af[8];
     const bf16* ap = ch + (int64_t)((live ? rb : 0) * 16 + lc) * FD + 8 * lq;
 #pragma unroll
@@ -992,7 +997,7 @@ __device__ __forceinline__ void xl_tile_s(const FusedArgs& a, const bf16* ch, co
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int g = rb * 16 + lq * 4 + r;
-        T.okg[r] = live && g < a.G;
+        T.okg[r] = RANGE ? live && g >= g0 && g < g1 : live && g < a.G;
         T.mraw[r] = T.okg[r] ? mimg[g] : 0.f;
     }
 #pragma unroll
@@ -1004,6 +1009,10 @@ __device__ __forceinline__ void xl_tile_s(const FusedArgs& a, const bf16* ch, co
             for (int ks = 0; ks < 8; ++ks) c = mfma16(af[ks], *(const bf16x8*)(bp + ks * 32), c);
 #pragma unroll
             for (int r = 0; r < 4; ++r) c[r] = fmaxf(c[r], 0.1f * c[r]);             // LeakyReLU(0.1), loss.py:236
+            if constexpr (RANGE) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) c[r] = T.okg[r] ? c[r] : 0.f;
+            }
         }
         T.S[nb] = c;
     }
@@ -1018,11 +1027,12 @@ __device__ __forceinline__ void xl_tile_s(const FusedArgs& a, const bf16* ch, co
     }
 }
 
-template <bool GROUND>
-__device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, int i, int j, float* out, const GroundOut& go) {
+template <bool GROUND, bool RANGE = false>
+__device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, int i, int j, float* out, const GroundOut& go, int g0 = 0, int g1 = 0) {
     const int tid = threadIdx.x, lane = tid & 63, lq = lane >> 4, lc = lane & 15;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nbg = a.Gr >> 4, nwb = a.Wp >> 4, nt = (nbg + 7) >> 3, nks2 = a.Wk >> 5;
+    const int nbg = a.Gr >> 4, nwb = a.Wp >> 4, nks2 = a.Wk >> 5;
+    const int t0 = RANGE ? g0 / LT : 0, nt = RANGE ? (g1 - 1) / LT + 1 : (nbg + 7) >> 3;        // the tiles [t0, nt) hold the regions scored
     bf16* Qs = (bf16*)(smem + LL_QS);
     bf16* P1s = (bf16*)(smem + LL_P1);
     bf16* P2s = (bf16*)(smem + LL_P2);
@@ -1036,7 +1046,7 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
     const float* mcap = a.mcap + (int64_t)j * a.W;
     const float* nc = a.nc + (int64_t)i * a.G;
     const float L2E = 1.4426950408889634f * a.lam;        // exp(lam x) = exp2(L2E x)
-    const float fG = (float)a.G, fW = (float)a.W;
+    const float fG = RANGE ? (float)(g1 - g0) : (float)a.G, fW = (float)a.W;
 
     // ---- Q^_j [Wp][256] -> LDS, kept for the whole pair; the k padding of the P2' tile (words Wp .. Wk-1) is zeroed once
     {
@@ -1063,9 +1073,9 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
     float csq[FW_MAXB], cs[FW_MAXB];
 #pragma unroll
     for (int nb = 0; nb < FW_MAXB; ++nb) { csq[nb] = 0.f; cs[nb] = 0.f; }
-    for (int t = 0; t < nt; ++t) {
+    for (int t = t0; t < nt; ++t) {
         TileRegs T;
-        xl_tile_s(a, ch, mimg, Qs, t * 8 + wid, L2E, T);
+        xl_tile_s<RANGE>(a, ch, mimg, Qs, t * 8 + wid, g0, g1, L2E, T);
 #pragma unroll
         for (int nb = 0; nb < FW_MAXB; ++nb) {
 #pragma unroll
@@ -1107,10 +1117,10 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
 #pragma unroll
     for (int nb = 0; nb < FW_MAXB; ++nb) { kw[nb] = 0ull; ew[nb] = 0.f; }
 
-    for (int t = 0; t < nt; ++t) {
+    for (int t = t0; t < nt; ++t) {
         const int rb = t * 8 + wid, row0 = wid * 16 + lq * 4;       // this lane's four rows of the tile: row0 .. row0 + 3
         TileRegs T;
-        xl_tile_s(a, ch, mimg, Qs, rb, L2E, T);
+        xl_tile_s<RANGE>(a, ch, mimg, Qs, rb, g0, g1, L2E, T);
         // image -> text: gated numerators of this block -> P1u tile [w][row], four consecutive regions per 8-byte write
 #pragma unroll
         for (int nb = 0; nb < FW_MAXB; ++nb) {
@@ -1176,10 +1186,15 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
         // requested after the barrier: 64 registers that the softmax passes above have no room for
         const int k0 = t * LT;
         const int nks1 = (a.Gk - k0) >> 5 < 4 ? (a.Gk - k0) >> 5 : 4;
+        // RANGE: a 32-region step wholly outside [g0, g1) has zeros in the P1u tile and is skipped (g1 <= Gk: a step inside is below nks1)
+        const auto ks1 = [&](int ks) {
+            if constexpr (RANGE) return k0 + ks * 32 < g1 && k0 + ks * 32 + 32 > g0;
+            else return ks < nks1;
+        };
         bf16x8 ca[2][4], qa[2][4];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const int k = ks < nks1 ? k0 + ks * 32 : 0;
+            const int k = ks1(ks) ? k0 + ks * 32 : 0;
             ca[0][ks] = *(const bf16x8*)(ct + k); ca[1][ks] = *(const bf16x8*)(ct + (int64_t)16 * a.Gk + k);
             const int kq = ks < nks2 ? ks * 32 : 0;
             qa[0][ks] = *(const bf16x8*)(qt + kq); qa[1][ks] = *(const bf16x8*)(qt + (int64_t)16 * a.Wk + kq);
@@ -1187,7 +1202,7 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
         // wc^T += C^^T_tile P1u_tile^T
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            if (ks < nks1) {
+            if (ks1(ks)) {
 #pragma unroll
                 for (int nb = 0; nb < FW_MAXB; ++nb) {
                     if (nb < nwb) {
@@ -1200,6 +1215,9 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
         }
         // |wc2_g|^2 of the tile's regions: wc2^T [d][g] = Q^^T [d][w] P2'^T, per-wave partials over this wave's 32 channels
         for (int gb = 0; gb < 8 && t * 8 + gb < nbg; ++gb) {
+            if constexpr (RANGE) {
+                if ((t * 8 + gb) * 16 >= g1 || (t * 8 + gb) * 16 + 16 <= g0) continue;      // no region of the range in this block
+            }
             f32x4 c0 = (f32x4){0.f, 0.f, 0.f, 0.f}, c1 = c0;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
@@ -1216,7 +1234,7 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
         }
         __syncthreads();                                   // the tiles are read; the partials are published
         // region cosines of the tile (loss.py:320-327), the eight partials summed in wave order
-        if (tid < LT && k0 + tid < a.G) {
+        if (tid < LT && (RANGE ? k0 + tid >= g0 && k0 + tid < g1 : k0 + tid < a.G)) {
             const int g = k0 + tid;
             float q = 0.f;
 #pragma unroll
@@ -1286,13 +1304,26 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
             go.word_weight[w] = wts[best * 112 + w] * ginv[w];
         }
     }
-    for (int g = tid; g < a.G; g += blockDim.x) part += rc[g] / fG;
+    if constexpr (RANGE) {
+        // the regions of the range (with g0 = 0, g1 = G: the loop below); a range without an unmasked region scores -inf, as an empty frame does
+        bool seen = false;
+        for (int g = g0 + tid; g < g1; g += blockDim.x) { part += rc[g] / fG; seen |= mimg[g] == 0.f; }
+        const int wseen = __ballot(seen) != 0ull;           // by the whole wave: inside the lane-0 branch it would see lane 0 alone
+        if (lane == 0) ((int*)xa)[wid] = wseen;
+    } else {
+        for (int g = tid; g < a.G; g += blockDim.x) part += rc[g] / fG;
+    }
     part = wave_sum(part);
     if (lane == 0) red[wid] = part;
     __syncthreads();
     if (tid == 0) {
         float t = 0.f;
         for (int w = 0; w < 8; ++w) t += red[w];
+        if constexpr (RANGE) {
+            int any = 0;
+            for (int w = 0; w < 8; ++w) any |= ((const int*)xa)[w];
+            if (!any) t = -__builtin_inff();
+        }
         *out = t;
     }
     if constexpr (GROUND) {
@@ -1341,6 +1372,22 @@ __global__ __launch_bounds__(512) void xl_index_pairs_ground_kernel(FusedArgs a,
         return;
     }
     xl_pair_score<true>(a, smem, i, j, a.scores + o, go);
+}
+
+// moments: workgroup (k M + m, j) -> scores[j][k][m], the frames [m stride, m stride + win) of video cand[j K + k] as a video
+// side of their own, read in place.  m is the fast grid axis: the windows of a pair run together and share its video in L2.
+__global__ __launch_bounds__(512) void xl_index_moments_kernel(FusedArgs a, int R, int win, int stride, int M) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int j = blockIdx.y, k = blockIdx.x / M, m = blockIdx.x - k * M;
+    const int64_t o = (int64_t)j * a.K + k;
+    const int i = a.cand[o];
+    float* out = a.scores + o * M + m;
+    if (i < 0 || i >= a.Bi) {
+        if (threadIdx.x == 0) *out = __builtin_nanf("");
+        return;
+    }
+    const int g0 = m * stride * R;
+    xl_pair_score<false, true>(a, smem, i, j, out, GroundOut{}, g0, g0 + win * R);
 }
 
 // resident CAPTION index, video-major pair list (the grid and hole rule of xf_caption_index_pairs_kernel, the body of xl_index_pairs_kernel):
@@ -1449,6 +1496,33 @@ extern "C" int dvlp_xattn_long_index_pairs_ground(int64_t capacity, int64_t G, c
     { static bool once = false; if (!once) { once = true;
         (void)hipFuncSetAttribute((const void*)xl_index_pairs_ground_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
     hipLaunchKernelGGL(xl_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bj), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream, a, go);
+    return dvlp_launch_status();
+}
+
+// ---- moments: every window of `win` frames at starts 0, stride, 2 stride, ... of the pairs of dvlp_xattn_long_index_pairs_fwd
+extern "C" int64_t dvlp_xattn_long_index_moments_count(int64_t G, int64_t frames, int64_t win, int64_t stride) {
+    if (G <= 0 || frames < 1 || frames > G || G % frames != 0 || win < 1 || win > frames || stride < 1) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, 1)) return DVLP_ERR_UNSUPPORTED;
+    return (frames - win) / stride + 1;
+}
+
+extern "C" int dvlp_xattn_long_index_moments_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                                 const void* Qraw, const float* mcap, int64_t K, const int* cand, int64_t frames, int64_t win,
+                                                 int64_t stride, float lam, int gate, float* scores, void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != FD || capacity <= 0 || capacity > INT32_MAX || G <= 0 || Bj <= 0 || W <= 0 || K <= 0) return DVLP_ERR_SHAPE;
+    if (Bj > 65535 || Bj * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mimg || !Qraw || !mcap || !cand || !scores || !workspace) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    const int64_t M = dvlp_xattn_long_index_moments_count(G, frames, win, stride);
+    if (M < 0) return (int)M;
+    if (K * M > INT32_MAX || Bj * K * M > INT32_MAX) return DVLP_ERR_SHAPE;      // the (window, candidate) grid axis; the score offsets
+    FusedArgs a = xf_index_prep(capacity, G, index, mimg, Bj, W, Qraw, mcap, K, cand, lam, gate & 1, scores, workspace, (hipStream_t)stream);
+    a.stop = 0;
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xl_index_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xl_index_moments_kernel, dim3((unsigned)(K * M), (unsigned)Bj), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream, a,
+                       (int)(G / frames), (int)win, (int)stride, (int)M);
     return dvlp_launch_status();
 }
 

@@ -911,6 +911,24 @@ def xattn_long_index_pairs_ground(index, capacity, G, m_img, Q, m_cap, cand, lam
     return out
 
 
+def xattn_long_index_moments_fwd(index, capacity, G, m_img, Q, m_cap, cand, frames, win, stride, lam, gate):
+    """The pairs of ``xattn_long_index_pairs_fwd`` scored on every window of ``win`` consecutive frames (``frames`` divides G; starts 0,
+    ``stride``, 2 ``stride``, ...) instead of the whole video: scores fp32 [Bj, K, M], entry m the local similarity of the regions of frames
+    [m stride, m stride + win) alone (``dvlp_xattn_long_index_moments_fwd``: the index is read in place, one launch).  A window without an
+    unmasked region scores -inf; an entry of cand outside [0, capacity) gives NaN in all M scores.  ``win = frames`` equals
+    ``xattn_long_index_pairs_fwd`` bit for bit.  Forward only."""
+    _long_pairs_checks(m_img, Q, m_cap, cand, capacity, G)
+    M = _size("dvlp_xattn_long_index_moments_count", int(G), int(frames), int(win), int(stride))
+    require_gpu(index, m_img, Q, m_cap, cand)
+    Bj, W, d = Q.shape
+    K = cand.shape[1]
+    ws = torch.empty(_size("dvlp_xattn_long_index_query_workspace_bytes", Bj, W), device=Q.device, dtype=torch.uint8)
+    scores = torch.empty((Bj, K, M), device=Q.device, dtype=torch.float32)
+    call("dvlp_xattn_long_index_moments_fwd", int(capacity), int(G), p(index), p(m_img), Bj, W, d, p(Q), p(m_cap), K, p(cand), int(frames),
+         int(win), int(stride), float(lam), _gate_bits(gate) & 1, p(scores), p(ws), stream())
+    return scores
+
+
 def xattn_caption_index_bytes(capacity, W):
     """Bytes of the prepared (resident) caption side of ``capacity`` captions of W words each; raises outside the fused kernel's range."""
     return _size("dvlp_xattn_caption_index_bytes", int(capacity), int(W))

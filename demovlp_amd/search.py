@@ -37,6 +37,11 @@ long QUERY videos: the resident caption side is byte for byte that of a fused in
 pair kernel on the video-major grid (``dvlp_xattn_long_caption_index_pairs_fwd`` / ``_pairs_ground``), bit-equal per pair to
 ``VideoIndex(..., tiled=True)``.
 
+Moments.  ``VideoIndex.moments`` / ``search(..., frames=F, moments=(4, 8))`` say WHEN a long video matched: every window of that many
+consecutive frames of a result is scored as a video of its own -- the local similarity of its regions alone, not a mean of whole-video
+cosines -- by ``dvlp_xattn_long_index_moments_fwd``, which reads the window out of the resident index in place (one launch
+per window length over all windows of all pairs), and the best window per result is picked on the device.  ``tiled=True`` indexes only.
+
 fp32 models, and region counts beyond the fused kernel's range (G > 288) without ``tiled=True``, take the parity route: the raw local
 embeddings are kept and each query's shortlist is gathered and scored by the multi-kernel ``RWALoss.get_sim`` -- slow and exact, as fp32 is
 everywhere in this package.
@@ -54,6 +59,25 @@ _DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16, torch.float32: 
 TOPK_MAX = 1024               # dvlp_topk_rows: 1 <= K <= 1024
 QUERY_BLOCK = 1024            # queries per pass of the pipeline (bounds the text tower's and the pair kernel's scratch)
 VIDEO_BLOCK = 256             # query videos per pass of CaptionIndex's pipeline (the object tower runs G + 1 tokens per video, not 100)
+
+
+def moment_windows(frames, windows, stride=1):
+    """The windows ``VideoIndex.moments`` scores, on the host: (starts, lengths), int64 tensors [M_total] in frames.  ``windows``: a window
+    length or a sequence of them; lengths come in the order given, starts 0, ``stride``, 2 ``stride``, ... ascending within a length
+    (``dvlp_xattn_long_index_moments_count`` windows each).  ValueError for what that entry refuses: a length outside [1, frames],
+    ``stride < 1``, no length at all."""
+    frames, stride = int(frames), int(stride)
+    lengths = [int(windows)] if isinstance(windows, (int, np.integer)) else [int(w) for w in windows]
+    if frames < 1 or stride < 1 or not lengths:
+        raise ValueError(f"frames and stride must be positive and windows not empty, got frames = {frames}, stride = {stride}, windows = {windows!r}")
+    starts, lens = [], []
+    for win in lengths:
+        M = call("dvlp_xattn_long_index_moments_count", frames, frames, win, stride)       # (G = frames: one region per frame)
+        if M < 0:
+            raise ValueError(f"a window of {win} frames does not fit a video of {frames} frames (1 <= window <= frames)")
+        starts += [m * stride for m in range(M)]
+        lens += [win] * M
+    return torch.tensor(starts, dtype=torch.int64), torch.tensor(lens, dtype=torch.int64)
 
 
 class _ResidentIndex:
@@ -284,11 +308,74 @@ class VideoIndex(_ResidentIndex):
                 model.train()
         return {name: torch.cat([r[name] for r in res]) for name in res[0]}
 
-    def search(self, model, loss_fn, text, k=10, shortlist=100, chunk=65536, ground=False, frames=None):
+    # ---- moments ------------------------------------------------------------------------------------------------------
+    def _moment_checks(self, frames, windows, stride):
+        """-> (starts, lengths, the window lengths as a list) on the host, or the error that names what is wrong"""
+        if not self.tiled:
+            raise DemoVLPHipError("moments need a bf16 index built with tiled=True (G <= 1152): the region-range pair kernel "
+                                  f"(dvlp_xattn_long_index_moments_fwd) is the tiled kernel's; this index is {self.dtype} with G = {self.G}")
+        if frames is None or int(frames) < 1 or self.G % int(frames) != 0:
+            raise ValueError(f"frames = {frames} must be a positive divisor of G = {self.G}")
+        starts, lengths = moment_windows(frames, windows, stride)
+        return starts, lengths, [int(windows)] if isinstance(windows, (int, np.integer)) else [int(w) for w in windows]
+
+    def _moments_block(self, loss_fn, side, ids, frames, windows, stride):
+        """Moments of one block's pairs (query j, index row ids[j, p]) from its text-tower outputs: one launch per window length, then the
+        best window per pair by ``dvlp_topk_rows`` (ties: the smaller position -- the earlier length, then the earlier start)."""
+        local_loss = getattr(loss_fn, "local_loss", loss_fn)
+        _, lt, text_mask = side
+        starts, lengths, wins = windows
+        lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
+        cand = ids.to(torch.int32).contiguous()
+        scores = torch.cat([ops.xattn_long_index_moments_fwd(self.local, self.capacity, self.G, self.om, lt, text_mask, cand, int(frames), w,
+                                                             int(stride), lam, gate) for w in wins], dim=2)
+        Nq, k, M = scores.shape
+        val, pos = ops.topk_rows(scores.view(Nq * k, M), 1)
+        val, pos = val.view(Nq, k), pos.view(Nq, k).long()
+        hole = torch.isnan(val)
+        start, length = starts.to(scores.device), lengths.to(scores.device)
+        minus = torch.full_like(pos, -1)
+        at = pos.clamp(0, M - 1)
+        return dict(scores=scores, start=start, length=length, best=torch.where(hole, minus, pos), best_start=torch.where(hole, minus, start[at]),
+                    best_length=torch.where(hole, minus, length[at]), best_score=val)
+
+    def moments(self, model, loss_fn, text, ids, frames, windows, stride=1):
+        """WHEN (query j, index row ``ids[j, p]``) matched: every window of ``windows`` (a length or a sequence of lengths, in frames) at
+        starts 0, ``stride``, ... of a video of ``frames`` frames (a divisor of G: regions are frame-major) scored as a video of its own --
+        the local similarity of its regions alone; the global cosine, which does not depend on the window, is not added.  ``ids`` int
+        [Nq, k], typically what ``search`` returned.  -> a dict on the device: ``scores`` fp32 [Nq, k, M_total] (-inf for a window without
+        an unmasked region), ``start`` / ``length`` int64 [M_total] (``moment_windows``), ``best`` int64 [Nq, k] (position of the best
+        window; equal scores: the earlier length, then the earlier start) and ``best_start`` / ``best_length`` / ``best_score`` [Nq, k].
+        An id outside the index gives NaN scores, NaN ``best_score`` and -1 in ``best`` / ``best_start`` / ``best_length``.  A window of
+        all ``frames`` frames scores what ``ground`` reports as ``score``, bit for bit.  ``tiled=True`` indexes only; no gradient flows."""
+        win = self._moment_checks(frames, windows, stride)
+        ids_in = text["input_ids"]
+        if not (ids_in.is_cuda and ids.is_cuda):
+            raise DemoVLPHipError("VideoIndex.moments runs on an MI355X device only (no CPU fallback): move the queries and ids to cuda")
+        if ids.dim() != 2 or ids.shape[0] != ids_in.shape[0] or ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"ids must be int [Nq = {ids_in.shape[0]}, k], got {ids.dtype} {tuple(ids.shape)}")
+        if self.n == 0:
+            raise ValueError("the index is empty")
+        was_training = model.training
+        model.eval()
+        res = []
+        try:
+            with torch.no_grad():
+                for q0 in range(0, ids_in.shape[0], QUERY_BLOCK):
+                    block = {name: t[q0:q0 + QUERY_BLOCK] for name, t in text.items() if isinstance(t, torch.Tensor)}
+                    res.append(self._moments_block(loss_fn, self._text_side(model, block), ids[q0:q0 + QUERY_BLOCK], frames, win, stride))
+        finally:
+            if was_training:
+                model.train()
+        return _cat_moments(res)
+
+    def search(self, model, loss_fn, text, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1):
         """The ``k`` best videos for every query of ``text`` (``{'input_ids', 'attention_mask'}`` [Nq, L] on the device) ->
         ``(ids int64 [Nq, k], scores fp32 [Nq, k])`` on the device, best first, equal scores by smaller id; ids are index rows.
         With ``ground=True``: ``(ids, scores, grounding)``, the dict of ``VideoIndex.ground`` for the k winners (one more launch over them,
-        on the text-tower outputs the search used; ``frames`` as there).
+        on the text-tower outputs the search used; ``frames`` as there).  With ``moments`` (window lengths in frames; needs ``frames`` and
+        a ``tiled=True`` index): the dict of ``VideoIndex.moments`` for the k winners at stride ``moment_stride``, computed on the same
+        text-tower outputs, is appended as the last element of the tuple.
 
         ``loss_fn`` supplies ``lambda_softmax`` / ``focal_type`` (a ``GlobalLocalLoss`` or its ``RWALoss``).  ``shortlist``: videos per query
         that reach the local stage, chosen by cosine (at most 1024); ``None`` or ``>= len(index)`` scores every video (exact search).
@@ -298,6 +385,7 @@ class VideoIndex(_ResidentIndex):
         k, S, chunk = self._search_checks(k, shortlist, chunk)
         if ground:
             self._ground_checks(frames)
+        win = self._moment_checks(frames, moments, moment_stride) if moments is not None else None
         ids_in = text["input_ids"]
         if not ids_in.is_cuda:
             raise DemoVLPHipError("VideoIndex.search runs on an MI355X device only (no CPU fallback): move the queries to cuda")
@@ -312,14 +400,22 @@ class VideoIndex(_ResidentIndex):
                     _, ids, cos, local = self._score(model, loss_fn, block, S, chunk, side)
                     val, pos = ops.topk_rows(cos + local, k)
                     top = torch.gather(ids, 1, pos.long()).long()
-                    res.append((top, val, self._ground_block(loss_fn, side, block["attention_mask"], top, frames) if ground else None))
+                    res.append((top, val, self._ground_block(loss_fn, side, block["attention_mask"], top, frames) if ground else None,
+                                self._moments_block(loss_fn, side, top, frames, win, moment_stride) if win is not None else None))
         finally:
             if was_training:
                 model.train()
-        ids, scores = torch.cat([r[0] for r in res]), torch.cat([r[1] for r in res])
-        if not ground:
-            return ids, scores
-        return ids, scores, {name: torch.cat([r[2][name] for r in res]) for name in res[0][2]}
+        out = (torch.cat([r[0] for r in res]), torch.cat([r[1] for r in res]))
+        if ground:
+            out += ({name: torch.cat([r[2][name] for r in res]) for name in res[0][2]},)
+        if win is not None:
+            out += (_cat_moments([r[3] for r in res]),)
+        return out
+
+
+def _cat_moments(res):
+    """the moments dicts of consecutive query blocks as one (``start`` / ``length`` describe the windows, not the queries)"""
+    return {name: res[0][name] if name in ("start", "length") else torch.cat([r[name] for r in res]) for name in res[0]}
 
 
 class CaptionIndex(_ResidentIndex):

@@ -282,6 +282,28 @@ int dvlp_xattn_long_index_pairs_ground(int64_t capacity, int64_t G, const void* 
                                        float* score, float* word_scores, float* region_scores, int* word_region, float* word_region_weight,
                                        int* region_word, float* frame_scores, void* workspace, void* stream);
 
+/* Moments of a long video (no reference counterpart): the pairs of dvlp_xattn_long_index_pairs_fwd scored on every window of
+   `win` consecutive frames instead of the whole video.  A video of G regions has `frames` frames of R = G / frames regions, frame-major;
+   window m covers the frames [m stride, m stride + win), i.e. the regions [g0, g1) = [m stride R, (m stride + win) R), and
+     scores[j][k][m] = the local similarity of (video cand[j K + k] restricted to the regions [g0, g1), caption j)
+   -- the pair score of the family above with C[g0:g1], m_img[g0:g1] as the video side: the means run over the win R regions of the window
+   and all W words, the focal gate of image->text compares against 1 / (win R).  The global cosine is not part of it.  A window without an
+   unmasked region (m_img != 0 on all of it) scores -inf.  The index is read in place -- a window is rows g0 .. g1 of chat, columns g0 .. g1
+   of chatT and entries g0 .. g1 of nc -- by one workgroup per (window, pair), all M windows of all pairs in one launch; nothing is resident
+   beyond the index of dvlp_xattn_long_index_bytes / _add, and the workspace is dvlp_xattn_long_index_query_workspace_bytes(Bj, W).
+     dvlp_xattn_long_index_moments_count  host arithmetic: M = (frames - win) / stride + 1, or a negative DVLP_ERR_* when frames does not
+                                          divide G, win is outside [1, frames], stride < 1 or G is out of range.
+     dvlp_xattn_long_index_moments_fwd    scores fp32 [Bj][K][M].  Argument rules of dvlp_xattn_long_index_pairs_fwd (DVLP_ERR_SHAPE /
+                                          DVLP_ERR_UNSUPPORTED before anything is launched, null pointers refused; K M <= 2^31 - 1); what
+                                          _moments_count refuses is refused here with its code.  A cand entry outside [0, capacity) reads
+                                          nothing: NaN in all M scores of that pair.
+   With win = frames (M = 1) the score equals dvlp_xattn_long_index_pairs_fwd's bit for bit.  No float atomics; every cross-wave sum is taken
+   in a fixed order: two runs give equal bytes. */
+int64_t dvlp_xattn_long_index_moments_count(int64_t G, int64_t frames, int64_t win, int64_t stride);
+int dvlp_xattn_long_index_moments_fwd(int64_t capacity, int64_t G, const void* index, const float* mimg, int64_t Bj, int64_t W, int64_t d,
+                                      const void* Qraw, const float* mcap, int64_t K, const int* cand, int64_t frames, int64_t win,
+                                      int64_t stride, float lam, int gate, float* scores, void* workspace, void* stream);
+
 /* Resident caption index + video-major pair list (video-to-text search, demovlp_amd/search.py): the family above with the roles swapped.
    The index is caller-owned device memory of dvlp_xattn_caption_index_bytes(capacity, W) bytes holding, per caption of W words, what the
    fused kernel's prep writes per call: qhat [Wp][256] and qhatT [256][Wk] in bf16 (Wp = W rounded up to 16, Wk = to 32) and the word norms
