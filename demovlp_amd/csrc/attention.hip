@@ -628,7 +628,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 const uint8_t* kr = a.keep + (((int64_t)b * a.H + h) * a.Ns + qi) * a.Ns;
 #pragma unroll
                 for (int kt = 0; kt < NKT; ++kt) {
-                    const uint32_t kw = *(const uint32_t*)(kr + 16 * kt + 4 * g);
+                    // <3,3> serves every L <= 48 with Ns = 16 / 32 / 48: a key tile at or past the row stride has no keep bytes (its
+                    // probabilities are exactly 0 -- padded keys carry -inf); reading them would run into the following rows and, for the
+                    // last rows of the last (batch, head), past the allocation.  Wave-uniform.
+                    const uint32_t kw = 16 * kt < a.Ns ? *(const uint32_t*)(kr + 16 * kt + 4 * g) : 0u;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) st[kt][qt][r] *= ((kw >> (8 * r)) & 1u) ? a.kscale : 0.f;
                 }

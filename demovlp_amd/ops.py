@@ -446,7 +446,9 @@ def space_attention_bwd(qkv, addmask, dout, B, F, R, out=None, stats=None, colsu
 def full_attention_fwd(q, k, v, addmask, B, L, ld=768, keep=None):
     """``ld``: row stride of q / k / v (2304 when they are the three column blocks of one packed projection).
     ``keep``: (keep bytes [B*H, Ns, Ns], transposed keep bytes, 1 / (1 - p)) from :func:`attn_keep_masks` -- dropout of the
-    attention probabilities."""
+    attention probabilities.
+    Accepted: ``1 <= L <= 128`` (the entry refuses anything else); in bf16 ``ld`` and the output's row stride must be multiples of 8
+    (16-byte row accesses).  Every sample needs at least one unmasked key (the CLS position always is)."""
     out = torch.empty((B * L, 768), device=q.device, dtype=q.dtype)
     ext = AttnExt(keep=keep[0].data_ptr(), keepT=keep[1].data_ptr(), keep_scale=float(keep[2])) if keep is not None else AttnExt()
     call("dvlp_attention_fwd_ex", dt(q), 1, B, L, HEADS, 1, L, p(q), p(k), p(v), ld, p(addmask), p(out), 768, SCALE, None, None, ctypes.byref(ext), stream())
@@ -454,6 +456,10 @@ def full_attention_fwd(q, k, v, addmask, B, L, ld=768, keep=None):
 
 
 def full_attention_bwd(q, k, v, addmask, dout, B, L, ld=768, out=None, ld_out=768, keep=None):
+    """Gradients (dq, dk, dv) of :func:`full_attention_fwd`, recomputed from q / k / v.  ``out``: three destinations of row stride ``ld_out``
+    (the column blocks of one [B*L, 2304] buffer with ``ld_out=2304``), allocated here when None.  ``keep``: the forward's masks.
+    Accepted: ``1 <= L <= 128`` (the entry refuses anything else); in bf16 ``ld``, ``ld_out`` and the row stride of ``dout`` (768 here) must
+    be multiples of 8 -- the matrix-core kernels read and write 16-byte row pieces (other strides take the slow generic kernel)."""
     ext = AttnExt(keep=keep[0].data_ptr(), keepT=keep[1].data_ptr(), keep_scale=float(keep[2])) if keep is not None else AttnExt()
     if out is None:
         dq, dk, dv = (torch.empty((B * L, 768), device=q.device, dtype=q.dtype) for _ in range(3))

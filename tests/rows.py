@@ -18,6 +18,7 @@ ROWS = {
     "test_size_helpers_run_on_host": "b",
     "test_product_reads_no_developer_variable": "b",
     "test_bad_arguments_are_reported_not_launched": "b",
+    "test_attention_and_keep_mask_entries_refuse_what_they_do_not_serve": "b A8",
     "test_no_reference_or_oracle_import_in_product": "b c",
     "test_gemm_plan_matches_recorded_dispatch": "b A3 A5",
     # ---- tests/test_boundary_init.py
@@ -86,6 +87,12 @@ ROWS = {
     "test_gemm_fused_column_sums": "A3 A5",
     "test_gemm_resident_b_batched_against_the_tile_kernel_and_fp32": "A10",
     "test_region_select_edge_counts": "A1",
+    # ---- tests/test_gpu_text_attention.py
+    "test_text_attention_vs_float64": "A8",
+    "test_packed_projection_equals_three_tensors": "A8",
+    "test_all_ones_keep_masks_equal_no_masks": "A8",
+    "test_run_to_run_identical": "A8",
+    "test_outputs_stay_inside_their_rows": "A8",
     # ---- tests/test_gpu_model.py
     "test_graft_entry_smoke_runs_and_checks_against_the_oracle": "b d",
     "test_fp32_forward_backward_vs_reference_golden": "A2 A3 A4 A5 A6 A7 A8 A9 A10 A11",

@@ -127,6 +127,32 @@ def test_bad_arguments_are_reported_not_launched(lib):
         lib.call("dvlp_layernorm_fwd", lib.F32, 4, 100, None, None, None, 1e-6, None, None, None, None, None)
 
 
+def test_attention_and_keep_mask_entries_refuse_what_they_do_not_serve(lib):
+    """Text attention (mode 1) serves 1 <= N <= 128 keys with R == N; there is no mode 2; a keep mask needs p < 1 and N >= 1.  Each is refused
+    on the host with the status that names the reason (null pointers: nothing may be launched), by the `_ex` entries and the plain ones."""
+    def fwd(entry, mode, N, R, ext=True):
+        tail = (None, None) if ext else (None,)                         # (ext,) stream
+        return lib.call(entry, lib.BF16, mode, 2, N, 12, 1, R, None, None, None, 768, None, None, 768, 0.125, None, None, *tail)
+
+    def bwd(entry, mode, N, R, ext=True):
+        tail = (None, None) if ext else (None,)
+        return lib.call(entry, lib.BF16, mode, 2, N, 12, 1, R, None, None, None, 768, None, None, 768, None, None, None, 768, None, 0.125, None, 0,
+                        None, *tail)
+
+    for run, entry, ext in ((fwd, "dvlp_attention_fwd_ex", True), (bwd, "dvlp_attention_bwd_ex", True),
+                            (fwd, "dvlp_attention_fwd", False), (bwd, "dvlp_attention_bwd", False)):
+        with pytest.raises(lib.DemoVLPHipError, match="bad shape"):
+            run(entry, 1, 129, 129, ext)                                # more keys than the kernels stage
+        with pytest.raises(lib.DemoVLPHipError, match="bad shape"):
+            run(entry, 1, 100, 99, ext)                                 # R != N
+        with pytest.raises(lib.DemoVLPHipError, match="not supported"):
+            run(entry, 2, 100, 100, ext)                                # no such mode
+    with pytest.raises(lib.DemoVLPHipError, match="bad shape"):
+        lib.call("dvlp_dropout_attn_mask", 36, 100, 1.0, None, 0, None, None, None)
+    with pytest.raises(lib.DemoVLPHipError, match="bad shape"):
+        lib.call("dvlp_dropout_attn_mask", 36, 0, 0.1, None, 0, None, None, None)
+
+
 def test_no_reference_or_oracle_import_in_product():
     """The shipped package must never import the oracle (or /root/reference)."""
     pkg = os.path.join(ROOT, "demovlp_amd")
