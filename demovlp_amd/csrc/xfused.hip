@@ -1027,7 +1027,27 @@ __device__ __forceinline__ void xl_tile_s(const FusedArgs& a, const bf16* ch, co
     }
 }
 
-template <bool GROUND, bool RANGE = false>
+// Q^_j [Wp][256] -> LDS, kept for the whole pair; the k padding of the P2' tile (words Wp .. Wk-1) is zeroed once.  Published by the first
+// barrier of xl_pair_score.
+__device__ __forceinline__ void xl_stage_q(const FusedArgs& a, char* smem, int j) {
+    const int tid = threadIdx.x;
+    bf16* Qs = (bf16*)(smem + LL_QS);
+    bf16* P2s = (bf16*)(smem + LL_P2);
+    const bf16* q = a.qhat + (int64_t)j * a.Wp * FD;
+    for (int p = tid; p < a.Wp * 32; p += blockDim.x) {
+        const int r = p >> 5, c = (p & 31) * 8;
+        *(bf16x8*)(Qs + r * FQS + c) = *(const bf16x8*)(q + r * FD + c);
+    }
+    if (a.Wk > a.Wp)
+        for (int p = tid; p < LT * (a.Wk - a.Wp); p += blockDim.x) P2s[(p / (a.Wk - a.Wp)) * LPS + a.Wp + p % (a.Wk - a.Wp)] = (bf16)0.f;
+}
+
+// STAGED (xl_caption_index_moments_kernel): the caller has run xl_stage_q for caption j and calls this once per window of its
+// chunk.  Nothing else differs: the barrier below publishes the staging for the first window and, for every later one, separates the
+// previous window's last LDS reads (thread 0: red and the flags in xa) from this window's first writes.  What a window reads of LDS it has
+// written itself -- the P1u / P2' tiles whole per tile (a block outside the range writes zeros), the exchange slots, nw2p, dotw, ginv, red
+// whole, dotg / rc at the regions of its own range -- except Q^ and the k padding of the P2' tile, which no window writes.
+template <bool GROUND, bool RANGE = false, bool STAGED = false>
 __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, int i, int j, float* out, const GroundOut& go, int g0 = 0, int g1 = 0) {
     const int tid = threadIdx.x, lane = tid & 63, lq = lane >> 4, lc = lane & 15;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1048,16 +1068,7 @@ __device__ __forceinline__ void xl_pair_score(const FusedArgs& a, char* smem, in
     const float L2E = 1.4426950408889634f * a.lam;        // exp(lam x) = exp2(L2E x)
     const float fG = RANGE ? (float)(g1 - g0) : (float)a.G, fW = (float)a.W;
 
-    // ---- Q^_j [Wp][256] -> LDS, kept for the whole pair; the k padding of the P2' tile (words Wp .. Wk-1) is zeroed once
-    {
-        const bf16* q = a.qhat + (int64_t)j * a.Wp * FD;
-        for (int p = tid; p < a.Wp * 32; p += blockDim.x) {
-            const int r = p >> 5, c = (p & 31) * 8;
-            *(bf16x8*)(Qs + r * FQS + c) = *(const bf16x8*)(q + r * FD + c);
-        }
-        if (a.Wk > a.Wp)
-            for (int p = tid; p < LT * (a.Wk - a.Wp); p += blockDim.x) P2s[(p / (a.Wk - a.Wp)) * LPS + a.Wp + p % (a.Wk - a.Wp)] = (bf16)0.f;
-    }
+    if constexpr (!STAGED) xl_stage_q(a, smem, j);
     float mc[FW_MAXB], mcraw[FW_MAXB];       // exponent offset lam log2(e) (m_cap - 1), m_cap = -1e4 for pad columns; m_cap itself
     bool okw[FW_MAXB];
 #pragma unroll
@@ -1405,6 +1416,34 @@ __global__ __launch_bounds__(512) void xl_caption_index_pairs_kernel(FusedArgs a
     xl_pair_score<false>(a, smem, i, j, a.scores + o, GroundOut{});
 }
 
+// moments of a query video against the resident captions: workgroup (k nch + c, i) -> the windows [c wpg, min(M, (c + 1) wpg))
+// of the pair (video i, caption cand[i K + k]).  The caption is staged once and the windows of the chunk are scored in turn, each by the
+// code of xl_index_moments_kernel (xl_pair_score<false, true>) on the regions [m stride R, (m stride + win) R) of video i in the per-call
+// workspace.  scores[(i K + k) M + m], window-major: scores[(i M + m) K + k].  The chunks of a pair are neighbours on the fast grid axis and
+// blockIdx.y is the video, so the workgroups in flight together share video i in L2, as in xl_caption_index_pairs_kernel.
+__global__ __launch_bounds__(512) void xl_caption_index_moments_kernel(FusedArgs a, int R, int win, int stride, int M, int wpg, int nch, int wmajor) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int i = blockIdx.y, k = blockIdx.x / nch, c = blockIdx.x - k * nch;
+    const int64_t o = (int64_t)i * a.K + k;
+    const int j = a.cand[o];
+    const int m0 = c * wpg, m1 = m0 + wpg < M ? m0 + wpg : M;
+    float* out = a.scores + (wmajor ? (int64_t)i * M * a.K + k : o * M);
+    const int64_t sm = wmajor ? a.K : 1;
+    if (j < 0 || j >= a.Bj) {
+        for (int m = m0 + threadIdx.x; m < m1; m += blockDim.x) out[m * sm] = __builtin_nanf("");
+        return;
+    }
+    xl_stage_q(a, smem, j);
+    for (int m = m0; m < m1; ++m) {
+        // the pair is made opaque per window: what xl_pair_score derives from (i, j) alone -- operand pointers, the caption's mask
+        // registers -- is then derived inside the loop, as in the one-window kernel, instead of being hoisted and held live across it
+        int iw = i, jw = j;
+        asm volatile("" : "+s"(iw), "+s"(jw));
+        const int g0 = m * stride * R;
+        xl_pair_score<false, true, true>(a, smem, iw, jw, out + m * sm, GroundOut{}, g0, g0 + win * R);
+    }
+}
+
 // the same grid with grounding: rows laid out [Bi][K][...]; an index outside [0, capacity) reads nothing: NaN in the float rows, -1 in the
 // int rows
 __global__ __launch_bounds__(512) void xl_caption_index_pairs_ground_kernel(FusedArgs a, GroundOut go) {
@@ -1582,5 +1621,42 @@ extern "C" int dvlp_xattn_long_caption_index_pairs_ground(int64_t capacity, int6
         (void)hipFuncSetAttribute((const void*)xl_caption_index_pairs_ground_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
     hipLaunchKernelGGL(xl_caption_index_pairs_ground_kernel, dim3((unsigned)K, (unsigned)Bi), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream, a,
                        go);
+    return dvlp_launch_status();
+}
+
+// ---- moments of a query video against the resident captions: the windows of dvlp_xattn_long_index_moments_fwd on the pairs of
+//      dvlp_xattn_long_caption_index_pairs_fwd, up to windows_per_group consecutive windows of a pair per workgroup
+// windows per workgroup when the caller leaves it open: host arithmetic on (Bi, K, M) alone.  One workgroup fits a CU (150 KB of LDS) and
+// the chip has 256 of them: when the pairs alone fill it, a workgroup walks all M windows of its pair and the caption is staged once per
+// pair; below that the windows are cut into just enough chunks to give every CU a workgroup.
+static int64_t xl_moments_plan(int64_t Bi, int64_t K, int64_t M) {
+    const int64_t pairs = Bi * K, cus = 256;
+    if (pairs >= cus) return M;
+    const int64_t want = (cus + pairs - 1) / pairs;             // chunks per pair that fill the chip
+    const int64_t n = M / want;                                 // (floor: at least `want` chunks)
+    return n < 1 ? 1 : n;
+}
+
+extern "C" int dvlp_xattn_long_caption_index_moments_fwd(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G,
+                                                         int64_t d, const void* Craw, const float* mimg, int64_t K, const int* cand, int64_t frames,
+                                                         int64_t win, int64_t stride, int64_t windows_per_group, int window_major, float lam,
+                                                         int gate, float* scores, void* workspace, void* stream) {
+    dvlp_clear_status();
+    if (d != FD || capacity <= 0 || capacity > INT32_MAX || W <= 0 || Bi <= 0 || G <= 0 || K <= 0 || windows_per_group < 0) return DVLP_ERR_SHAPE;
+    if (Bi > 65535 || Bi * K > INT32_MAX) return DVLP_ERR_SHAPE;
+    if (!index || !mcap || !Craw || !mimg || !cand || !scores || !workspace) return DVLP_ERR_SHAPE;
+    if (!xlong_ok(G, W)) return DVLP_ERR_UNSUPPORTED;
+    const int64_t M = dvlp_xattn_long_index_moments_count(G, frames, win, stride);
+    if (M < 0) return (int)M;
+    if (K * M > INT32_MAX || Bi * K * M > INT32_MAX) return DVLP_ERR_SHAPE;      // the (chunk, candidate) grid axis; the score offsets
+    int64_t wpg = windows_per_group ? windows_per_group : xl_moments_plan(Bi, K, M);
+    if (wpg > M) wpg = M;
+    const int64_t nch = (M + wpg - 1) / wpg;
+    FusedArgs a = xf_caption_index_prep(capacity, W, index, mcap, Bi, G, Craw, mimg, K, cand, lam, gate & 1, scores, workspace, (hipStream_t)stream);
+    a.stop = 0;
+    { static bool once = false; if (!once) { once = true;
+        (void)hipFuncSetAttribute((const void*)xl_caption_index_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } }
+    hipLaunchKernelGGL(xl_caption_index_moments_kernel, dim3((unsigned)(K * nch), (unsigned)Bi), dim3(512), (size_t)LL_TOTAL, (hipStream_t)stream,
+                       a, (int)(G / frames), (int)win, (int)stride, (int)M, (int)wpg, (int)nch, window_major ? 1 : 0);
     return dvlp_launch_status();
 }

@@ -1052,6 +1052,30 @@ def xattn_long_caption_index_pairs_ground(index, capacity, W, m_cap, C, m_img, c
     return out
 
 
+def xattn_long_caption_index_moments_fwd(index, capacity, W, m_cap, C, m_img, cand, frames, win, stride, lam, gate, window_major=False,
+                                         windows_per_group=0):
+    """The pairs of ``xattn_long_caption_index_pairs_fwd`` scored on every window of ``win`` consecutive frames of the query video
+    (``frames`` divides G; starts 0, ``stride``, 2 ``stride``, ...): scores fp32 [Bi, K, M] -- with ``window_major`` [Bi, M, K] -- entry
+    (i, k, m) the local similarity of the regions of frames [m stride, m stride + win) of video i alone against caption cand[i, k]
+    (``dvlp_xattn_long_caption_index_moments_fwd``), bit-equal to ``xattn_long_index_moments_fwd`` on the same pair and window.
+    ``windows_per_group``: consecutive windows of a pair one workgroup scores with its caption staged once (0: the library's planner
+    chooses); it changes no byte of the result.  A window without an unmasked region scores -inf; an entry of cand outside [0, capacity)
+    gives NaN in all M scores.  ``win = frames`` equals ``xattn_long_caption_index_pairs_fwd`` bit for bit.  Forward only."""
+    if C.dim() == 3:                 # (host arithmetic, so a bad window is named before the device is asked for; else the shape check below speaks)
+        M = _size("dvlp_xattn_long_index_moments_count", int(C.shape[1]), int(frames), int(win), int(stride))
+    if int(windows_per_group) < 0:
+        raise _lib.DemoVLPHipError(f"windows_per_group must be 0 (the planner chooses) or positive, got {windows_per_group}")
+    _caption_index_checks(index, capacity, W, m_cap, C, m_img, cand)
+    Bi, G, d = C.shape
+    K = cand.shape[1]
+    ws = torch.empty(_size("dvlp_xattn_long_caption_index_query_workspace_bytes", Bi, G, int(W)), device=C.device, dtype=torch.uint8)
+    scores = torch.empty((Bi, M, K) if window_major else (Bi, K, M), device=C.device, dtype=torch.float32)
+    call("dvlp_xattn_long_caption_index_moments_fwd", int(capacity), int(W), p(index), p(m_cap), Bi, G, d, p(C), p(m_img), K, p(cand),
+         int(frames), int(win), int(stride), int(windows_per_group), int(bool(window_major)), float(lam), _gate_bits(gate) & 1, p(scores),
+         p(ws), stream())
+    return scores
+
+
 def topk_rows(x, K, N=None, index_base=0, out=None, merge=False):
     """x fp32 [M, ld] (first N columns; default all) -> (val fp32 [M, K], idx int32 [M, K]): per row the K largest values in descending order,
     ties by smaller index (np.argsort(-x, kind="stable")[:, :K] + index_base), NaN last, (-inf, -1) where N < K.  ``out`` = (val, idx) to write

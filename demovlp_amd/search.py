@@ -41,6 +41,11 @@ Moments.  ``VideoIndex.moments`` / ``search(..., frames=F, moments=(4, 8))`` say
 consecutive frames of a result is scored as a video of its own -- the local similarity of its regions alone, not a mean of whole-video
 cosines -- by ``dvlp_xattn_long_index_moments_fwd``, which reads the window out of the resident index in place (one launch
 per window length over all windows of all pairs), and the best window per result is picked on the device.  ``tiled=True`` indexes only.
+``CaptionIndex.moments`` / ``search(..., frames=F, moments=(4, 8))`` are the same question for a long QUERY video against resident
+captions -- the same windows, the same scores bit for bit -- on ``dvlp_xattn_long_caption_index_moments_fwd``, where a
+workgroup stages its caption once and walks the windows of its pair.  ``CaptionIndex.timeline`` turns it round: for every window of a query
+video the ``k`` best captions of the video's shortlist by that window's local similarity (the kernel's window-major output, one
+``dvlp_topk_rows`` over all windows) -- which captions apply when.
 
 fp32 models, and region counts beyond the fused kernel's range (G > 288) without ``tiled=True``, take the parity route: the raw local
 embeddings are kept and each query's shortlist is gathered and scored by the multi-kernel ``RWALoss.get_sim`` -- slow and exact, as fp32 is
@@ -329,15 +334,7 @@ class VideoIndex(_ResidentIndex):
         cand = ids.to(torch.int32).contiguous()
         scores = torch.cat([ops.xattn_long_index_moments_fwd(self.local, self.capacity, self.G, self.om, lt, text_mask, cand, int(frames), w,
                                                              int(stride), lam, gate) for w in wins], dim=2)
-        Nq, k, M = scores.shape
-        val, pos = ops.topk_rows(scores.view(Nq * k, M), 1)
-        val, pos = val.view(Nq, k), pos.view(Nq, k).long()
-        hole = torch.isnan(val)
-        start, length = starts.to(scores.device), lengths.to(scores.device)
-        minus = torch.full_like(pos, -1)
-        at = pos.clamp(0, M - 1)
-        return dict(scores=scores, start=start, length=length, best=torch.where(hole, minus, pos), best_start=torch.where(hole, minus, start[at]),
-                    best_length=torch.where(hole, minus, length[at]), best_score=val)
+        return _best_moments(scores, starts, lengths)
 
     def moments(self, model, loss_fn, text, ids, frames, windows, stride=1):
         """WHEN (query j, index row ``ids[j, p]``) matched: every window of ``windows`` (a length or a sequence of lengths, in frames) at
@@ -411,6 +408,19 @@ class VideoIndex(_ResidentIndex):
         if win is not None:
             out += (_cat_moments([r[3] for r in res]),)
         return out
+
+
+def _best_moments(scores, starts, lengths):
+    """the moments dict of window scores [N, k, M_total]: the best window per pair by ``dvlp_topk_rows`` (K = 1; a hole's NaN row: -1 / NaN)"""
+    Nq, k, M = scores.shape
+    val, pos = ops.topk_rows(scores.view(Nq * k, M), 1)
+    val, pos = val.view(Nq, k), pos.view(Nq, k).long()
+    hole = torch.isnan(val)
+    start, length = starts.to(scores.device), lengths.to(scores.device)
+    minus = torch.full_like(pos, -1)
+    at = pos.clamp(0, M - 1)
+    return dict(scores=scores, start=start, length=length, best=torch.where(hole, minus, pos), best_start=torch.where(hole, minus, start[at]),
+                best_length=torch.where(hole, minus, length[at]), best_score=val)
 
 
 def _cat_moments(res):
@@ -619,11 +629,108 @@ class CaptionIndex(_ResidentIndex):
                 model.train()
         return {name: torch.cat([r[name] for r in res]) for name in res[0]}
 
-    def search(self, model, loss_fn, data, k=10, shortlist=100, chunk=65536, ground=False, frames=None):
+    # ---- moments ------------------------------------------------------------------------------------------------------
+    def _moment_checks(self, frames, windows, stride, G):
+        """-> (starts, lengths, the window lengths as a list) on the host for query videos of G regions, or the error that names what is wrong"""
+        if not self.tiled:
+            raise DemoVLPHipError("moments need a bf16 index built with tiled=True (W <= 112): the region-range pair kernel "
+                                  f"(dvlp_xattn_long_caption_index_moments_fwd) is the tiled kernel's; this index is {self.dtype} with W = {self.W}")
+        if frames is None or int(frames) < 1 or G % int(frames) != 0:
+            raise ValueError(f"frames = {frames} must be a positive divisor of G = {G}")
+        starts, lengths = moment_windows(frames, windows, stride)
+        return starts, lengths, [int(windows)] if isinstance(windows, (int, np.integer)) else [int(w) for w in windows]
+
+    def _window_scores(self, loss_fn, side, ids, frames, wins, stride, window_major):
+        """one launch per window length over all windows of the pairs (video i, index row ids[i, p]), concatenated along the window axis"""
+        local_loss = getattr(loss_fn, "local_loss", loss_fn)
+        _, lo, om = side
+        lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
+        cand = ids.to(torch.int32).contiguous()
+        return torch.cat([ops.xattn_long_caption_index_moments_fwd(self.local, self.capacity, self.W, self.tm, lo, om, cand, int(frames), w,
+                                                                   int(stride), lam, gate, window_major=window_major) for w in wins],
+                         dim=1 if window_major else 2)
+
+    def _moments_block(self, loss_fn, side, ids, frames, windows, stride):
+        """Moments of one block's pairs (video i, index row ids[i, p]) from its object-tower outputs: one launch per window length, then the
+        best window per pair by ``dvlp_topk_rows`` (ties: the smaller position -- the earlier length, then the earlier start)."""
+        starts, lengths, wins = windows
+        return _best_moments(self._window_scores(loss_fn, side, ids, frames, wins, stride, False), starts, lengths)
+
+    def moments(self, model, loss_fn, data, ids, frames, windows, stride=1):
+        """WHEN (video i, index row ``ids[i, p]``) matched: every window of ``windows`` (a length or a sequence of lengths, in frames) at
+        starts 0, ``stride``, ... of the query videos of ``frames`` frames (a divisor of their G: regions are frame-major) scored as a video
+        of its own against the caption -- the local similarity of its regions alone; the global cosine, which does not depend on the window,
+        is not added.  ``data`` = ``{'object', 'object_mask'}`` on the device, ``ids`` int [Nv, k], typically what ``search`` returned.
+        -> the dict of ``VideoIndex.moments`` on the device: ``scores`` fp32 [Nv, k, M_total] (-inf for a window without an unmasked
+        region), ``start`` / ``length`` int64 [M_total] (``moment_windows``), ``best`` int64 [Nv, k] (position of the best window; equal
+        scores: the earlier length, then the earlier start) and ``best_start`` / ``best_length`` / ``best_score`` [Nv, k].  An id outside
+        the index gives NaN scores, NaN ``best_score`` and -1 in ``best`` / ``best_start`` / ``best_length``.  Each score equals, bit for
+        bit, what ``VideoIndex.moments`` gives for the same pair and window.  ``tiled=True`` indexes only; no gradient flows."""
+        obj = data["object"]
+        win = self._moment_checks(frames, windows, stride, int(obj.shape[1] * obj.shape[2]))
+        if ids.dim() != 2 or ids.shape[0] != obj.shape[0] or ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"ids must be int [Nv = {obj.shape[0]}, k], got {ids.dtype} {tuple(ids.shape)}")
+        if self.n == 0:
+            raise ValueError("the index is empty")
+        if not (obj.is_cuda and ids.is_cuda):
+            raise DemoVLPHipError("CaptionIndex.moments runs on an MI355X device only (no CPU fallback): move the videos and ids to cuda")
+        was_training = model.training
+        model.eval()
+        res = []
+        try:
+            with torch.no_grad():
+                for v0, block in self._blocks(data):
+                    res.append(self._moments_block(loss_fn, self._video_side(model, block), ids[v0:v0 + VIDEO_BLOCK], frames, win, stride))
+        finally:
+            if was_training:
+                model.train()
+        return _cat_moments(res)
+
+    def timeline(self, model, loss_fn, data, frames, windows, stride=1, k=5, shortlist=100, chunk=65536):
+        """WHICH captions apply WHEN: for every window of ``windows`` (as in ``moments``) of every query video of ``data``, the ``k`` best
+        captions of the video's cosine shortlist (``shortlist`` captions chosen by the whole video's cosine, at most 1024; ``None`` or
+        ``>= len(index)``: every caption), ranked by the window's local similarity alone -- the whole-video cosine does not depend on the
+        window and is not added.  One window-major launch of ``dvlp_xattn_long_caption_index_moments_fwd`` per window length, then one
+        ``dvlp_topk_rows`` over the [Nv M_total, S] rows.  -> a dict on the device: ``ids`` int64 [Nv, M_total, k] (index rows),
+        ``scores`` fp32 [Nv, M_total, k], ``cosine`` fp32 [Nv, M_total, k] (the shortlist cosine of each returned caption, for a caller
+        who wants to add a prior) and ``start`` / ``length`` int64 [M_total] (``moment_windows``).  Best first; equal scores go to the
+        smaller index row.  A window without an unmasked region gives ``scores`` = -inf, ``ids`` = -1 and ``cosine`` = NaN.  The checks on
+        ``k``, ``shortlist`` and ``chunk`` are those of ``search``.  ``tiled=True`` indexes only; no gradient flows."""
+        k, S, chunk = self._search_checks(k, shortlist, chunk)
+        obj = data["object"]
+        starts, lengths, wins = self._moment_checks(frames, windows, stride, int(obj.shape[1] * obj.shape[2]))
+        if not obj.is_cuda:
+            raise DemoVLPHipError("CaptionIndex.timeline runs on an MI355X device only (no CPU fallback): move the videos to cuda")
+        was_training = model.training
+        model.eval()
+        res = []
+        try:
+            with torch.no_grad():
+                for _, block in self._blocks(data):
+                    side = self._video_side(model, block)
+                    ids, cos = self._global_stage(ops.rownorm_fwd(side[0].contiguous())[0], S, chunk)          # ids ascending per row
+                    scores = self._window_scores(loss_fn, side, ids, frames, wins, stride, True)                # [Nv, M_total, S]
+                    Nv, M = scores.shape[:2]
+                    val, pos = ops.topk_rows(scores.view(Nv * M, S), k)
+                    val, pos = val.view(Nv, M, k), pos.view(Nv, M, k).long().clamp(min=0)
+                    empty = torch.isneginf(val)
+                    top = torch.gather(ids.long()[:, None, :].expand(Nv, M, S), 2, pos)
+                    prior = torch.gather(cos[:, None, :].expand(Nv, M, S), 2, pos)
+                    res.append((torch.where(empty, torch.full_like(top, -1), top), val,
+                                torch.where(empty, torch.full_like(prior, float("nan")), prior)))
+        finally:
+            if was_training:
+                model.train()
+        return dict(ids=torch.cat([r[0] for r in res]), scores=torch.cat([r[1] for r in res]), cosine=torch.cat([r[2] for r in res]),
+                    start=starts.to(obj.device), length=lengths.to(obj.device))
+
+    def search(self, model, loss_fn, data, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1):
         """The ``k`` best captions for every video of ``data`` (``{'object', 'object_mask'}`` on the device) ->
         ``(ids int64 [Nv, k], scores fp32 [Nv, k])`` on the device, best first, equal scores by smaller id; ids are index rows.
         With ``ground=True``: ``(ids, scores, grounding)``, the dict of ``CaptionIndex.ground`` for the k winners (one more launch over them,
-        on the object-tower outputs the search used; ``frames`` as there).
+        on the object-tower outputs the search used; ``frames`` as there).  With ``moments`` (window lengths in frames; needs ``frames`` and
+        a ``tiled=True`` index): the dict of ``CaptionIndex.moments`` for the k winners at stride ``moment_stride``, computed on the same
+        object-tower outputs, is appended as the last element of the tuple.
 
         ``loss_fn`` supplies ``lambda_softmax`` / ``focal_type`` (a ``GlobalLocalLoss`` or its ``RWALoss``).  ``shortlist``: captions per
         video that reach the local stage, chosen by cosine (at most 1024); ``None`` or ``>= len(index)`` scores every caption (exact search).
@@ -635,6 +742,7 @@ class CaptionIndex(_ResidentIndex):
         obj = data["object"]
         if ground:
             self._ground_checks(frames, int(obj.shape[1] * obj.shape[2]))
+        win = self._moment_checks(frames, moments, moment_stride, int(obj.shape[1] * obj.shape[2])) if moments is not None else None
         if not obj.is_cuda:
             raise DemoVLPHipError("CaptionIndex.search runs on an MI355X device only (no CPU fallback): move the videos to cuda")
         was_training = model.training
@@ -647,14 +755,17 @@ class CaptionIndex(_ResidentIndex):
                     _, ids, cos, local = self._score(model, loss_fn, block, S, chunk, side)
                     val, pos = ops.topk_rows(cos + local, k)
                     top = torch.gather(ids, 1, pos.long()).long()
-                    res.append((top, val, self._ground_block(loss_fn, side, top, frames) if ground else None))
+                    res.append((top, val, self._ground_block(loss_fn, side, top, frames) if ground else None,
+                                self._moments_block(loss_fn, side, top, frames, win, moment_stride) if win is not None else None))
         finally:
             if was_training:
                 model.train()
-        ids, scores = torch.cat([r[0] for r in res]), torch.cat([r[1] for r in res])
-        if not ground:
-            return ids, scores
-        return ids, scores, {name: torch.cat([r[2][name] for r in res]) for name in res[0][2]}
+        out = (torch.cat([r[0] for r in res]), torch.cat([r[1] for r in res]))
+        if ground:
+            out += ({name: torch.cat([r[2][name] for r in res]) for name in res[0][2]},)
+        if win is not None:
+            out += (_cat_moments([r[3] for r in res]),)
+        return out
 
 
 def two_stage_sims(global_sims, ids, scores):

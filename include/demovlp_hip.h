@@ -353,6 +353,25 @@ int dvlp_xattn_long_caption_index_pairs_ground(int64_t capacity, int64_t W, cons
                                                int gate, float* score, float* word_scores, float* region_scores, int* word_region,
                                                float* word_region_weight, int* region_word, float* frame_scores, void* workspace, void* stream);
 
+/* Moments of a long QUERY video against the resident caption index (no reference counterpart): the windows of
+   dvlp_xattn_long_index_moments_fwd on the pairs of dvlp_xattn_long_caption_index_pairs_fwd.  Window m of video i covers the frames
+   [m stride, m stride + win), i.e. the regions [m stride R, (m stride + win) R) with R = G / frames, and its score is the local similarity
+   of (video i restricted to those regions, caption cand[i K + k]) -- bit for bit what dvlp_xattn_long_index_moments_fwd gives for that
+   pair and window from a video index of the same videos.  M = dvlp_xattn_long_index_moments_count(G, frames, win, stride).
+     windows_per_group  0: the host planner chooses (arithmetic on Bi, K, M alone); n >= 1: each workgroup stages its caption once and scores
+                        up to n consecutive windows of one pair in turn; negative: DVLP_ERR_SHAPE.  Every window's arithmetic is independent
+                        of the chunking: the scores are byte-identical for every value.
+     window_major       0: scores fp32 [Bi][K][M]; 1: scores fp32 [Bi][M][K] (rows for a per-window top-k over the captions).
+   The argument lists and rules are those of the two parent entries: DVLP_ERR_SHAPE / DVLP_ERR_UNSUPPORTED before anything is launched, null
+   pointers refused, Bi <= 65535, Bi K M <= 2^31 - 1, and what _moments_count refuses is refused with its code.  A cand entry outside
+   [0, capacity) reads nothing: NaN in all M scores of that pair, in either layout.  A window without an unmasked region scores -inf.
+   Nothing new is resident; workspace: dvlp_xattn_long_caption_index_query_workspace_bytes(Bi, G, W).  With win = frames the score equals
+   dvlp_xattn_long_caption_index_pairs_fwd's bit for bit.  No float atomics: two runs give equal bytes. */
+int dvlp_xattn_long_caption_index_moments_fwd(int64_t capacity, int64_t W, const void* index, const float* mcap, int64_t Bi, int64_t G, int64_t d,
+                                              const void* Craw, const float* mimg, int64_t K, const int* cand, int64_t frames, int64_t win,
+                                              int64_t stride, int64_t windows_per_group, int window_major, float lam, int gate, float* scores,
+                                              void* workspace, void* stream);
+
 /* ---- row top-k (csrc/topk.hip; no reference counterpart: the reference ranks on the host, model/metric.py) ----
    Per row m of the fp32 matrix x [M][ld] (first N columns): val[m][0..K) = the K largest values, descending, idx[m][..] = their column numbers
    + index_base (int32).  Total order: larger value first, equal values by smaller index -- np.argsort(-x, kind="stable")[:K]; -0.0 == +0.0; a NaN
