@@ -18,6 +18,9 @@
 // sorted K-list to the workspace and topk_merge_kernel -- one workgroup per row, the same selector fed from lists instead of columns --
 // picks the row's K out of the S lists.  merge = 1 adds the K entries already in val / idx as one more list: the same pass, so chunked
 // calls equal the one-shot call bit for bit.
+//
+// Mask.  dvlp_topk_rows_masked is the same scan with an allow bit per GLOBAL column (index_base + column): a disallowed column offers word 0,
+// so it is deleted, not merely ranked last -- it can neither be listed nor raise the threshold.  The merge pass is unchanged.
 #include "common.h"
 
 constexpr int TK_THREADS = 256, TK_ROUND = 4 * TK_THREADS, TK_MAXK = 1024, TK_CAP = TK_MAXK + TK_ROUND, TK_MAXSEG = 256;
@@ -101,8 +104,16 @@ __device__ __forceinline__ void tk_emit(TopkSel& s, int K, unsigned* __restrict_
     }
 }
 
-// workgroup (m, s): columns [s seg, min(N, (s + 1) seg)) of row m -> list (m, s)
+// workgroup (m, s): columns [s seg, min(N, (s + 1) seg)) of row m -> list (m, s).  MASKED: column c takes part iff bit (index_base + c) & 31 of
+// word (index_base + c) >> 5 of the row's allow mask is set; a disallowed column offers word 0 ("none"), like a column beyond N.  A thread's
+// four columns are consecutive, so their bits sit in one or two words: those of its first and last column inside [lo, hi), fetched with the
+// 16-byte load (the next round's are in flight with it) and read as one 64-bit field.  Only words (index_base + lo) >> 5 ..
+// (index_base + hi - 1) >> 5 are loaded.  The unmasked instantiation is the kernel as it was: every masked line is under `if constexpr`.
+struct TopkLoad { f32x4 v; u64 bits; };
+
+template <bool MASKED>
 __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(int64_t N, const float* __restrict__ x, int64_t ld, int K, int64_t index_base, int S, int64_t seg,
+                                                               const unsigned* __restrict__ allow, int64_t allow_ld,
                                                                unsigned* __restrict__ oval, int* __restrict__ oidx) {
     __shared__ TopkSel s;
     const int tid = threadIdx.x;
@@ -115,26 +126,42 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(int64_t N, const 
     const int64_t base = lo - ((lo + off) & 3);
     const int64_t rounds = (hi - base + TK_ROUND - 1) / TK_ROUND;
     tk_init(s);
-    auto load = [&](int64_t rd) -> f32x4 {
+    auto load = [&](int64_t rd) -> TopkLoad {
         const int64_t q = base + rd * TK_ROUND + tid * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (q >= lo && q + 3 < hi) v = __builtin_nontemporal_load((const f32x4*)(xr + q));
+        TopkLoad L;
+        L.v = f32x4{0.f, 0.f, 0.f, 0.f};
+        L.bits = 0ull;
+        if (q >= lo && q + 3 < hi) L.v = __builtin_nontemporal_load((const f32x4*)(xr + q));
         else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) if (q + e >= lo && q + e < hi) v[e] = xr[q + e];
+            for (int e = 0; e < 4; ++e) if (q + e >= lo && q + e < hi) L.v[e] = xr[q + e];
         }
-        return v;
+        if constexpr (MASKED) {
+            const int64_t c0 = q > lo ? q : lo, c1 = q + 3 < hi ? q + 3 : hi - 1;      // the thread's columns inside [lo, hi)
+            if (c0 <= c1) {
+                const unsigned* ar = allow + m * allow_ld;
+                const int64_t w0 = (index_base + c0) >> 5, w1 = (index_base + c1) >> 5;
+                const unsigned a0 = ar[w0];
+                L.bits = (u64)a0 | ((u64)(w1 != w0 ? ar[w1] : a0) << 32);
+            }
+        }
+        return L;
     };
-    f32x4 cur = load(0);
+    TopkLoad cur = load(0);
     for (int64_t rd = 0; rd < rounds; ++rd) {
-        f32x4 nxt = {0.f, 0.f, 0.f, 0.f};
+        TopkLoad nxt;
+        nxt.v = f32x4{0.f, 0.f, 0.f, 0.f};
+        nxt.bits = 0ull;
         if (rd + 1 < rounds) nxt = load(rd + 1);
         const int64_t q = base + rd * TK_ROUND + tid * 4;
         u64 w[4]; unsigned r[4];
+        [[maybe_unused]] const int64_t bit0 = ((index_base + (q > lo ? q : lo)) >> 5) << 5;      // global column of bit 0 of cur.bits
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            r[e] = __float_as_uint(cur[e]);
-            w[e] = (q + e >= lo && q + e < hi) ? tk_word(r[e], (int)(index_base + q + e)) : 0ull;
+            r[e] = __float_as_uint(cur.v[e]);
+            bool in = q + e >= lo && q + e < hi;
+            if constexpr (MASKED) in = in && ((cur.bits >> (int)((index_base + q + e - bit0) & 63)) & 1ull);      // (in range: 0 .. 34)
+            w[e] = in ? tk_word(r[e], (int)(index_base + q + e)) : 0ull;
         }
         tk_offer(s, K, w, r);
         cur = nxt;
@@ -199,22 +226,41 @@ extern "C" int64_t dvlp_topk_workspace_bytes(int64_t M, int64_t N, int K) {
     return M * topk_plan(M, N, K).S * K * 8;
 }
 
-// x [M][ld] fp32 (first N columns) -> val [M][K] fp32, idx [M][K] int32; workspace: dvlp_topk_workspace_bytes(M, N, K)
-extern "C" int dvlp_topk_rows(int64_t M, int64_t N, const float* x, int64_t ld, int K, int64_t index_base, float* val, int* idx, int merge,
-                              void* workspace, void* stream) {
+static int topk_launch(int64_t M, int64_t N, const float* x, int64_t ld, int K, int64_t index_base, const unsigned* allow, int64_t allow_ld, bool masked,
+                       float* val, int* idx, int merge, void* workspace, void* stream) {
     dvlp_clear_status();
     const int rc = topk_check(M, N, K);
     if (rc != DVLP_OK) return rc;
     if (ld < N || index_base < 0 || index_base + N > INT32_MAX || (merge != 0 && merge != 1)) return DVLP_ERR_SHAPE;
     if (!x || !val || !idx || !workspace || ((uintptr_t)x & 3)) return DVLP_ERR_SHAPE;
+    // a mask row holds the bits of global columns 0 .. index_base + N - 1: allow_ld = 0 (one row for all) or at least that many words
+    if (masked && (!allow || ((uintptr_t)allow & 3) || allow_ld < 0 || (allow_ld != 0 && allow_ld < (index_base + N + 31) / 32))) return DVLP_ERR_SHAPE;
     const TopkPlan P = topk_plan(M, N, K);
     hipStream_t st = (hipStream_t)stream;
     const bool direct = P.S == 1 && !merge;
     unsigned* lval = (unsigned*)workspace;
     int* lidx = (int*)((char*)workspace + M * P.S * K * 4);
-    hipLaunchKernelGGL(topk_scan_kernel, dim3((unsigned)(M * P.S)), dim3(TK_THREADS), 0, st, N, x, ld, K, index_base, P.S, P.seg,
-                       direct ? (unsigned*)val : lval, direct ? idx : lidx);
+    const dim3 grid((unsigned)(M * P.S)), block(TK_THREADS);
+    if (masked)
+        hipLaunchKernelGGL(topk_scan_kernel<true>, grid, block, 0, st, N, x, ld, K, index_base, P.S, P.seg, allow, allow_ld,
+                           direct ? (unsigned*)val : lval, direct ? idx : lidx);
+    else
+        hipLaunchKernelGGL(topk_scan_kernel<false>, grid, block, 0, st, N, x, ld, K, index_base, P.S, P.seg, (const unsigned*)nullptr, (int64_t)0,
+                           direct ? (unsigned*)val : lval, direct ? idx : lidx);
     if (!direct)
         hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(TK_THREADS), 0, st, K, P.S, merge, lval, lidx, (unsigned*)val, idx);
     return dvlp_launch_status();
+}
+
+// x [M][ld] fp32 (first N columns) -> val [M][K] fp32, idx [M][K] int32; workspace: dvlp_topk_workspace_bytes(M, N, K)
+extern "C" int dvlp_topk_rows(int64_t M, int64_t N, const float* x, int64_t ld, int K, int64_t index_base, float* val, int* idx, int merge,
+                              void* workspace, void* stream) {
+    return topk_launch(M, N, x, ld, K, index_base, nullptr, 0, false, val, idx, merge, workspace, stream);
+}
+
+// the same with disallowed columns deleted: column c of row m takes part iff bit (index_base + c) & 31 of allow[m allow_ld + ((index_base + c) >> 5)]
+// is set (allow_ld = 0: one mask row for all M rows).  Entries merged in from val / idx passed the mask when they were selected.
+extern "C" int dvlp_topk_rows_masked(int64_t M, int64_t N, const float* x, int64_t ld, int K, int64_t index_base, const uint32_t* allow, int64_t allow_ld,
+                                     float* val, int* idx, int merge, void* workspace, void* stream) {
+    return topk_launch(M, N, x, ld, K, index_base, allow, allow_ld, true, val, idx, merge, workspace, stream);
 }

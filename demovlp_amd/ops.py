@@ -1076,10 +1076,7 @@ def xattn_long_caption_index_moments_fwd(index, capacity, W, m_cap, C, m_img, ca
     return scores
 
 
-def topk_rows(x, K, N=None, index_base=0, out=None, merge=False):
-    """x fp32 [M, ld] (first N columns; default all) -> (val fp32 [M, K], idx int32 [M, K]): per row the K largest values in descending order,
-    ties by smaller index (np.argsort(-x, kind="stable")[:, :K] + index_base), NaN last, (-inf, -1) where N < K.  ``out`` = (val, idx) to write
-    there; with ``merge`` their K entries take part as further candidates (streaming over column chunks)."""
+def _topk_args(x, K, N, out, merge):
     if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
         raise _lib.DemoVLPHipError(f"topk_rows expects an fp32 matrix with unit column stride, got {x.dtype} {tuple(x.shape)}")
     M, ld = x.shape[0], (x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1]))
@@ -1093,10 +1090,60 @@ def topk_rows(x, K, N=None, index_base=0, out=None, merge=False):
     if (val.dtype, idx.dtype) != (torch.float32, torch.int32) or tuple(val.shape) != (M, K) or tuple(idx.shape) != (M, K) \
             or not val.is_contiguous() or not idx.is_contiguous():
         raise _lib.DemoVLPHipError("out must be contiguous (fp32 [M, K], int32 [M, K])")
+    return M, ld, N, K, val, idx
+
+
+def topk_rows(x, K, N=None, index_base=0, out=None, merge=False):
+    """x fp32 [M, ld] (first N columns; default all) -> (val fp32 [M, K], idx int32 [M, K]): per row the K largest values in descending order,
+    ties by smaller index (np.argsort(-x, kind="stable")[:, :K] + index_base), NaN last, (-inf, -1) where N < K.  ``out`` = (val, idx) to write
+    there; with ``merge`` their K entries take part as further candidates (streaming over column chunks)."""
+    M, ld, N, K, val, idx = _topk_args(x, K, N, out, merge)
     nbytes = _size("dvlp_topk_workspace_bytes", M, N, K)
     require_gpu(x, val, idx)
     ws = torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
     call("dvlp_topk_rows", M, N, p(x), ld, K, int(index_base), p(val), p(idx), int(bool(merge)), p(ws), stream())
+    return val, idx
+
+
+_ALLOW_WORDS = (torch.int32, torch.uint32)
+
+
+def pack_allow_bits(allow):
+    """bool [n] or [M, n] -> the allow mask ``topk_rows_masked`` reads: uint32 words [ceil(n / 32)] or [M, ceil(n / 32)] on the same device, bit
+    ``c & 31`` of word ``c >> 5`` set iff ``allow[..., c]``; the bits beyond n in the last word are 0.  Plain torch ops (not a hot path: pack
+    a filter once, search with it many times)."""
+    if allow.dtype != torch.bool or allow.dim() not in (1, 2) or allow.shape[-1] < 1:
+        raise ValueError(f"pack_allow_bits expects a bool tensor [n] or [M, n] with n >= 1, got {allow.dtype} {tuple(allow.shape)}")
+    n = allow.shape[-1]
+    words = (n + 31) // 32
+    bits = torch.zeros(allow.shape[:-1] + (words * 32,), device=allow.device, dtype=torch.int64)
+    bits[..., :n] = allow
+    weight = torch.ones(32, device=allow.device, dtype=torch.int64) << torch.arange(32, device=allow.device, dtype=torch.int64)
+    v = (bits.view(allow.shape[:-1] + (words, 32)) * weight).sum(-1)                  # 0 .. 2^32 - 1
+    return torch.where(v >= 1 << 31, v - (1 << 32), v).to(torch.int32).view(torch.uint32)
+
+
+def topk_rows_masked(x, K, allow, N=None, index_base=0, out=None, merge=False):
+    """``topk_rows`` on each row with its disallowed columns deleted (``dvlp_topk_rows_masked``).  ``allow``: uint32 (or int32) words on the
+    device, [words] (one mask for all rows) or [M, words] with unit word stride (``pack_allow_bits``), addressed by GLOBAL column number:
+    column c takes part iff bit ``(index_base + c) & 31`` of word ``(index_base + c) >> 5`` is set, so a caller streaming over column chunks
+    passes the same mask with a moving ``index_base``; it must hold ``ceil((index_base + N) / 32)`` words.  A disallowed column is never
+    listed; rows with fewer than K allowed columns end in (-inf, -1).  ``out`` / ``merge`` as in ``topk_rows``: merged entries take part
+    unconditionally (they passed the mask when they were selected)."""
+    M, ld, N, K, val, idx = _topk_args(x, K, N, out, merge)
+    if not isinstance(allow, torch.Tensor) or allow.dtype not in _ALLOW_WORDS or allow.dim() not in (1, 2) or allow.stride(-1) != 1 \
+            or (allow.dim() == 2 and allow.shape[0] != M):
+        raise _lib.DemoVLPHipError(f"allow must be uint32 words [words] or [M = {M}, words] with unit word stride (ops.pack_allow_bits), got "
+                                   f"{getattr(allow, 'dtype', type(allow))} {tuple(getattr(allow, 'shape', ()))}")
+    if allow.shape[-1] * 32 < int(index_base) + N:
+        raise _lib.DemoVLPHipError(f"allow holds {allow.shape[-1] * 32} bits, the columns end at index_base + N = {int(index_base) + N}")
+    allow_ld = 0 if allow.dim() == 1 else (allow.stride(0) if M > 1 else allow.shape[1])
+    if 0 < allow_ld < allow.shape[-1]:                                                # (row stride 0, an expanded mask, is the shared form)
+        raise _lib.DemoVLPHipError("the rows of allow overlap")
+    nbytes = _size("dvlp_topk_workspace_bytes", M, N, K)
+    require_gpu(x, val, idx, allow)
+    ws = torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
+    call("dvlp_topk_rows_masked", M, N, p(x), ld, K, int(index_base), p(allow), int(allow_ld), p(val), p(idx), int(bool(merge)), p(ws), stream())
     return val, idx
 
 

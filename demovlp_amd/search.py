@@ -50,6 +50,15 @@ video the ``k`` best captions of the video's shortlist by that window's local si
 fp32 models, and region counts beyond the fused kernel's range (G > 288) without ``tiled=True``, take the parity route: the raw local
 embeddings are kept and each query's shortlist is gathered and scored by the multi-kernel ``RWALoss.get_sim`` -- slow and exact, as fp32 is
 everywhere in this package.
+
+Filters and removal.  ``search`` / ``shortlist_by_cosine`` / ``timeline`` take ``allow``, a bool tensor over the index rows
+(one for all queries or one per query): the global stage runs ``dvlp_topk_rows_masked``, which never lists a disallowed row, so the cut to
+``shortlist`` is made among the allowed rows -- filtering a larger result on the host would cut first and could leave nothing.  A query
+with fewer allowed rows than asked for is padded with id -1, the hole every later stage already knows (the pair kernels score it NaN, the
+final top-k sorts it last) and comes back as (-1, -inf).  ``index.remove(ids)`` clears the rows' bits in a resident ``alive`` mask (one bit
+per row, allocated at the first removal, ANDed into every filter) and zeroes their global embeddings; rows keep their numbers.
+``index.replace(rows, ...)`` overwrites rows in place through the ``*_index_add`` entries and revives them; ``index.live`` and
+``index.removed()`` count and list.  Compaction (renumbering rows) is not offered.
 """
 from __future__ import annotations
 
@@ -89,8 +98,85 @@ class _ResidentIndex:
     """What both directions share: the row count, the search-argument checks and the global (cosine) stage over ``self.gn`` [capacity, 256],
     the normalised global embeddings of the ``self.n`` resident rows."""
 
+    alive = None              # uint32 words [ceil(capacity / 32)], bit r = row r is live; allocated by the first ``remove`` (None: nothing was ever removed)
+
     def __len__(self):
         return self.n
+
+    # ---- filters and removal ------------------------------------------------------------------------------------------------
+    def _filter(self, allow, Nq):
+        """The packed allow mask of one call -> uint32 words [words] (every query) or [Nq, words] (per query), or None when no row is
+        left out: ``allow`` (bool [len(index)] or [Nq, len(index)] on the index's device, or None) ANDed with the live rows."""
+        if allow is None:
+            return self.alive
+        if not isinstance(allow, torch.Tensor) or allow.dtype != torch.bool or tuple(allow.shape) not in ((self.n,), (Nq, self.n)) \
+                or allow.device.type != self.device.type:
+            got = f"{allow.dtype} {tuple(allow.shape)} on {allow.device}" if isinstance(allow, torch.Tensor) else repr(type(allow))
+            raise ValueError(f"allow must be a bool tensor [{self.n}] (every query) or [{Nq}, {self.n}] (per query) on {self.device.type}: one entry "
+                             f"per index row; got {got}")
+        words = ops.pack_allow_bits(allow)
+        if self.alive is not None:
+            words = (words.view(torch.int32) & self.alive.view(torch.int32)[:words.shape[-1]]).view(torch.uint32)
+        return words
+
+    @staticmethod
+    def _rows_of(mask, q0, q1):
+        return mask if mask is None or mask.dim() == 1 else mask[q0:q1]
+
+    @classmethod
+    def _mask_arg(cls, mask, q0, q1):
+        """the ``mask`` keyword of ``_score`` for the queries [q0, q1); no keyword at all without a mask: that call is what it was"""
+        return {} if mask is None else {"mask": cls._rows_of(mask, q0, q1)}
+
+    def _row_list(self, rows, what):
+        """-> the rows of a ``remove`` / ``replace`` call as a list of ints, or the ValueError that names the one outside [0, len(index))"""
+        rows = [int(r) for r in (rows.tolist() if isinstance(rows, torch.Tensor) else rows)]
+        bad = [r for r in rows if r < 0 or r >= self.n]
+        if bad:
+            raise ValueError(f"{what}: row {bad[0]} is outside [0, len(index) = {self.n})")
+        return rows
+
+    def _set_alive(self, rows, on):
+        if self.alive is None:
+            if on:
+                return
+            full = torch.ones(self.capacity, device=self.gn.device, dtype=torch.bool)      # rows not yet in use are live: ``add`` needs no mask
+        else:
+            full = _unpack_bits(self.alive, self.capacity)
+        full[torch.tensor(rows, device=full.device, dtype=torch.int64)] = bool(on)
+        self.alive = ops.pack_allow_bits(full)
+
+    def remove(self, ids):
+        """Take the rows ``ids`` (ints in [0, len(index)); a list or a tensor) out of every later result: ``search``, ``shortlist_by_cosine``
+        and ``timeline`` never list them, ``ground`` / ``moments`` answer for them as for a hole (id -1).  Rows keep their numbers and
+        ``len(index)`` its value; a removed row's bytes stay where they are (``replace`` reuses the slot) but its global embedding is
+        zeroed, so a saved index does not carry it.  Removing a row twice is a no-op; an id outside the index is a ``ValueError``."""
+        rows = self._row_list(ids, "remove")
+        if not rows:
+            return self
+        with torch.no_grad():
+            self._set_alive(rows, False)
+            self.gn[torch.tensor(rows, device=self.gn.device, dtype=torch.int64)] = 0.0
+        return self
+
+    def removed(self):
+        """The removed rows, int64 ascending, on the index's device: the slots ``replace`` can reuse."""
+        if self.alive is None:
+            return torch.empty(0, device=self.device, dtype=torch.int64)
+        return torch.nonzero(~_unpack_bits(self.alive, self.n))[:, 0]
+
+    @property
+    def live(self):
+        """rows in use that were not removed (``len(index)`` counts the removed ones too)"""
+        return self.n - int(self.removed().numel())
+
+    def _live_ids(self, ids):
+        """explicit ids of ``ground`` / ``moments``: a removed row becomes -1, the hole every pair kernel answers NaN for"""
+        if self.alive is None:
+            return ids
+        inside = (ids >= 0) & (ids < self.capacity)
+        live = _unpack_bits(self.alive, self.capacity)[ids.long().clamp(0, self.capacity - 1)]
+        return torch.where(inside & ~live, torch.full_like(ids, -1), ids)
 
     def _shortlist_size(self, shortlist):
         return self.n if shortlist is None or shortlist >= self.n else int(shortlist)
@@ -109,23 +195,43 @@ class _ResidentIndex:
             raise ValueError(f"chunk must be positive, got {chunk}")
         return k, S, chunk
 
-    def _global_stage(self, qn, S, chunk):
-        """-> (ids int32 [Nq, S] ascending per row, cosines fp32 [Nq, S]) of the S best index rows per query by cosine."""
+    def _global_stage(self, qn, S, chunk, mask=None):
+        """-> (ids int32 [Nq, S] ascending per row, cosines fp32 [Nq, S]) of the S best index rows per query by cosine.  ``mask`` (``_filter``):
+        the S best ALLOWED rows (``dvlp_topk_rows_masked``: a disallowed row is never scored against the cut); a query with fewer than S
+        of them is padded with id -1 (cosine -inf; in the exact branch S == n the cosine of a left-out row stays, its id is -1), the hole
+        the later stages score NaN."""
         Nq, dev = qn.shape[0], qn.device
         if S == self.n:                                            # every row: nothing to select
             cos = torch.empty((Nq, self.n), device=dev, dtype=torch.float32)
             for c0 in range(0, self.n, chunk):
                 cn = min(chunk, self.n - c0)
                 ops.gemm(qn, self.gn[c0:], Nq, cn, 256, dtype=ops.F32, out=cos[:, c0:], ldc=self.n)
-            return torch.arange(self.n, device=dev, dtype=torch.int32).expand(Nq, -1).contiguous(), cos
+            ids = torch.arange(self.n, device=dev, dtype=torch.int32).expand(Nq, -1)
+            if mask is not None:
+                ids = torch.where(_unpack_bits(mask, self.n).expand(Nq, -1), ids, torch.full_like(ids, -1))
+            return ids.contiguous(), cos
         out = (torch.empty((Nq, S), device=dev, dtype=torch.float32), torch.empty((Nq, S), device=dev, dtype=torch.int32))
         for c0 in range(0, self.n, chunk):
             cn = min(chunk, self.n - c0)
             sims = ops.gemm(qn, self.gn[c0:], Nq, cn, 256, dtype=ops.F32)
-            ops.topk_rows(sims, S, index_base=c0, out=out, merge=c0 > 0)
+            if mask is None:
+                ops.topk_rows(sims, S, index_base=c0, out=out, merge=c0 > 0)
+            else:
+                ops.topk_rows_masked(sims, S, mask, index_base=c0, out=out, merge=c0 > 0)
         # by id: the final cut breaks score ties by position in the shortlist, which must then mean "smaller id first"
         ids, order = torch.sort(out[1], dim=1)
         return ids.contiguous(), torch.gather(out[0], 1, order).contiguous()
+
+
+def _unpack_bits(words, n):
+    """uint32 words [..., >= ceil(n / 32)] (``ops.pack_allow_bits``) -> bool [..., n]"""
+    c = torch.arange(n, device=words.device, dtype=torch.int64)
+    return ((words.view(torch.int32)[..., c >> 5] >> (c & 31).to(torch.int32)) & 1).bool()
+
+
+def _holes(top, val):
+    """the final cut of a filtered search: a hole (id -1, NaN score, sorted last) reads (-1, -inf)"""
+    return torch.where(top < 0, torch.full_like(val, float("-inf")), val)
 
 
 class VideoIndex(_ResidentIndex):
@@ -163,9 +269,8 @@ class VideoIndex(_ResidentIndex):
             self.local = torch.zeros((self.capacity, self.G, 256), device=dev, dtype=self.dtype)
 
     # ---- filling ------------------------------------------------------------------------------------------------------
-    def add(self, out):
-        """Append the videos of ``out``, the dict ``ObjectRelation.forward(..., return_embeds=True)`` returns (its ``global_object_embeddings``
-        [n, 256], ``local_object_embeddings`` [n, G, 256] and ``object_mask`` [n, G] are read).  Returns the index rows they took."""
+    def _checked(self, out, rows=None):
+        """the tensors of an ``add`` / ``replace`` (``rows``) call, checked -> (global, local, mask, n); allocates the device memory"""
         go, lo, om = out["global_object_embeddings"], out["local_object_embeddings"], out["object_mask"]
         n = go.shape[0]
         if lo.dim() != 3 or lo.shape[1] != self.G or lo.shape[2] != 256:
@@ -174,23 +279,49 @@ class VideoIndex(_ResidentIndex):
             raise ValueError(f"expected [n, 256], [n, {self.G}, 256], [n, {self.G}], got {tuple(go.shape)}, {tuple(lo.shape)}, {tuple(om.shape)}")
         if lo.dtype != self.dtype:
             raise ValueError(f"this index holds {self.dtype} embeddings, got {lo.dtype}")
-        if self.n + n > self.capacity:
+        if rows is None and self.n + n > self.capacity:
             raise ValueError(f"adding {n} videos to {self.n} exceeds the capacity {self.capacity}")
+        if rows is not None and len(rows) != n:
+            raise ValueError(f"replace: {len(rows)} rows for {n} videos")
         if not (go.is_cuda and lo.is_cuda and om.is_cuda):
             raise DemoVLPHipError("VideoIndex lives on an MI355X device only (no CPU fallback): embeddings must be on the device")
         self._alloc()
+        return go, lo, om, n
+
+    def _write(self, r0, go, lo, om):
+        n = go.shape[0]
+        self.gn[r0:r0 + n] = ops.rownorm_fwd(go.detach().contiguous())[0]
+        self.om[r0:r0 + n] = om.detach().float()
+        if self.tiled:
+            ops.xattn_long_index_add(self.local, self.capacity, self.G, r0, lo.detach().contiguous())
+        elif self.fused:
+            ops.xattn_index_add(self.local, self.capacity, self.G, r0, lo.detach().contiguous())
+        else:
+            self.local[r0:r0 + n] = lo.detach()
+
+    def add(self, out):
+        """Append the videos of ``out``, the dict ``ObjectRelation.forward(..., return_embeds=True)`` returns (its ``global_object_embeddings``
+        [n, 256], ``local_object_embeddings`` [n, G, 256] and ``object_mask`` [n, G] are read).  Returns the index rows they took."""
+        go, lo, om, n = self._checked(out)
         r0 = self.n
         with torch.no_grad():
-            self.gn[r0:r0 + n] = ops.rownorm_fwd(go.detach().contiguous())[0]
-            self.om[r0:r0 + n] = om.detach().float()
-            if self.tiled:
-                ops.xattn_long_index_add(self.local, self.capacity, self.G, r0, lo.detach().contiguous())
-            elif self.fused:
-                ops.xattn_index_add(self.local, self.capacity, self.G, r0, lo.detach().contiguous())
-            else:
-                self.local[r0:r0 + n] = lo.detach()
+            self._write(r0, go, lo, om)
         self.n += n
         return range(r0, r0 + n)
+
+    def replace(self, rows, out):
+        """Overwrite the index rows ``rows`` (ints in [0, len(index)), one per video of ``out``, the dict ``add`` takes) in place: a
+        re-encoded video, or a new one in a slot ``removed()`` lists.  The rows are written by the entry ``add`` uses
+        (``dvlp_xattn_index_add`` at ``row0 = r``), so a replaced row's bytes are those of a fresh index holding the same video; a removed
+        row is live again.  Returns ``self``."""
+        rows = self._row_list(rows, "replace")
+        go, lo, om, _ = self._checked(out, rows)
+        with torch.no_grad():
+            for i, r in enumerate(rows):
+                self._write(r, go[i:i + 1], lo[i:i + 1], om[i:i + 1])
+            if rows:
+                self._set_alive(rows, True)
+        return self
 
     def add_batches(self, model, batches):
         """Run the object tower only (``model.compute_object``) on every batch ``{'object', 'object_mask', ...}`` and add its videos."""
@@ -213,6 +344,8 @@ class VideoIndex(_ResidentIndex):
                      gn=self.gn.cpu(), om=self.om.cpu(), local=self.local.cpu())
         if self.tiled:      # (only tiled indexes write the key: every other state dict is what it was)
             state["tiled"] = True
+        if self.alive is not None:      # (the same pattern: written once something has been removed)
+            state["alive"] = self.alive.cpu()
         return state
 
     def load_state_dict(self, state):
@@ -223,19 +356,23 @@ class VideoIndex(_ResidentIndex):
         for name in ("gn", "om", "local"):
             getattr(self, name).copy_(state[name])
         self.n = int(state["n"])
+        self.alive = state["alive"].to(self.gn.device) if "alive" in state else None
         return self
 
     # ---- search -------------------------------------------------------------------------------------------------------
-    def shortlist_by_cosine(self, global_text_embeddings, shortlist, chunk=65536):
+    def shortlist_by_cosine(self, global_text_embeddings, shortlist, chunk=65536, allow=None):
         """The global stage alone: (ids int64 [Nq, S] ascending per row, cosines fp32 [Nq, S]) of the ``shortlist`` best videos per query
-        embedding [Nq, 256] by cosine (ties by smaller id)."""
+        embedding [Nq, 256] by cosine (ties by smaller id).  ``allow`` (bool [len(index)] or [Nq, len(index)] on the device; ``ValueError``
+        otherwise): only allowed rows, and never a removed one; a query with fewer than S of them starts with ids -1 (cosine -inf)."""
+        mask = self._filter(allow, global_text_embeddings.shape[0])
         if not global_text_embeddings.is_cuda or self.n == 0:
             raise DemoVLPHipError("shortlist_by_cosine needs a filled index and embeddings on an MI355X device")
         with torch.no_grad():
-            ids, cos = self._global_stage(ops.rownorm_fwd(global_text_embeddings.detach().contiguous())[0], self._shortlist_size(shortlist), int(chunk))
+            ids, cos = self._global_stage(ops.rownorm_fwd(global_text_embeddings.detach().contiguous())[0], self._shortlist_size(shortlist), int(chunk),
+                                          mask)
         return ids.long(), cos
 
-    def _local_stage(self, local_loss, lt, text_mask, ids):
+    def _local_stage(self, local_loss, lt, text_mask, ids, holes=False):
         lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
         if self.tiled:
             return Fn.XattnLongIndexPairsFn.apply(self.local, self.capacity, self.G, self.om, lt, text_mask, ids, lam, gate)
@@ -244,6 +381,13 @@ class VideoIndex(_ResidentIndex):
         out = torch.empty(ids.shape, device=ids.device, dtype=torch.float32)
         for j in range(ids.shape[0]):                              # parity route: the query's videos gathered, multi-kernel grid [S, 1]
             rows = ids[j].long()
+            if holes:                                              # a filtered search: the -1s of the query are dropped before the gather, NaN in their place
+                keep = rows >= 0
+                out[j] = float("nan")
+                if bool(keep.any()):
+                    rows = rows[keep]
+                    out[j, keep] = local_loss.get_sim(self.local[rows], lt[j:j + 1], self.om[rows], None, text_mask[j:j + 1])[:, 0]
+                continue
             out[j] = local_loss.get_sim(self.local[rows], lt[j:j + 1], self.om[rows], None, text_mask[j:j + 1])[:, 0]
         return out
 
@@ -258,13 +402,14 @@ class VideoIndex(_ResidentIndex):
             raise DemoVLPHipError(f"captions of {lt.shape[1]} words are beyond the fused kernel's range (W <= 112)")
         return gt, lt.contiguous(), text_mask
 
-    def _score(self, model, loss_fn, text, S, chunk, side=None):
-        """One block of queries through the text tower (or its outputs ``side``) and both stages -> (qn, ids int32 [Nq, S], cos, local)."""
+    def _score(self, model, loss_fn, text, S, chunk, side=None, mask=None):
+        """One block of queries through the text tower (or its outputs ``side``) and both stages -> (qn, ids int32 [Nq, S], cos, local);
+        ``mask``: the block's rows of ``_filter``."""
         local_loss = getattr(loss_fn, "local_loss", loss_fn)
         gt, lt, text_mask = side if side is not None else self._text_side(model, text)
         qn = ops.rownorm_fwd(gt.contiguous())[0]
-        ids, cos = self._global_stage(qn, S, chunk)
-        return qn, ids, cos, self._local_stage(local_loss, lt, text_mask, ids)
+        ids, cos = self._global_stage(qn, S, chunk, mask)
+        return qn, ids, cos, self._local_stage(local_loss, lt, text_mask, ids, mask is not None)
 
     def _ground_block(self, loss_fn, side, att, ids, frames):
         """Grounding of one block's pairs (query j, index row ids[j, p]) from its text-tower outputs."""
@@ -307,7 +452,8 @@ class VideoIndex(_ResidentIndex):
             with torch.no_grad():
                 for q0 in range(0, ids_in.shape[0], QUERY_BLOCK):
                     block = {name: t[q0:q0 + QUERY_BLOCK] for name, t in text.items() if isinstance(t, torch.Tensor)}
-                    res.append(self._ground_block(loss_fn, self._text_side(model, block), block["attention_mask"], ids[q0:q0 + QUERY_BLOCK], frames))
+                    res.append(self._ground_block(loss_fn, self._text_side(model, block), block["attention_mask"],
+                                                  self._live_ids(ids[q0:q0 + QUERY_BLOCK]), frames))
         finally:
             if was_training:
                 model.train()
@@ -360,13 +506,14 @@ class VideoIndex(_ResidentIndex):
             with torch.no_grad():
                 for q0 in range(0, ids_in.shape[0], QUERY_BLOCK):
                     block = {name: t[q0:q0 + QUERY_BLOCK] for name, t in text.items() if isinstance(t, torch.Tensor)}
-                    res.append(self._moments_block(loss_fn, self._text_side(model, block), ids[q0:q0 + QUERY_BLOCK], frames, win, stride))
+                    res.append(self._moments_block(loss_fn, self._text_side(model, block), self._live_ids(ids[q0:q0 + QUERY_BLOCK]), frames, win,
+                                                   stride))
         finally:
             if was_training:
                 model.train()
         return _cat_moments(res)
 
-    def search(self, model, loss_fn, text, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1):
+    def search(self, model, loss_fn, text, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1, allow=None):
         """The ``k`` best videos for every query of ``text`` (``{'input_ids', 'attention_mask'}`` [Nq, L] on the device) ->
         ``(ids int64 [Nq, k], scores fp32 [Nq, k])`` on the device, best first, equal scores by smaller id; ids are index rows.
         With ``ground=True``: ``(ids, scores, grounding)``, the dict of ``VideoIndex.ground`` for the k winners (one more launch over them,
@@ -378,12 +525,20 @@ class VideoIndex(_ResidentIndex):
         that reach the local stage, chosen by cosine (at most 1024); ``None`` or ``>= len(index)`` scores every video (exact search).
         ``chunk``: index rows per global-stage product.  The score is ``cos(text_j, video_i) + local(video_i, caption_j)``: in
         ``trainer.evaluate``'s terms ``global_sims + local_sims.T``, NOT its ``o2t_sims`` (which keeps the reference's transposed-addend
-        quirk), so metrics of search results are not comparable with the reference's evaluation numbers.  No gradient flows."""
+        quirk), so metrics of search results are not comparable with the reference's evaluation numbers.  No gradient flows.
+
+        ``allow``: a filter, bool on the device, [len(index)] (every query) or [Nq, len(index)] (per query); anything else is a
+        ``ValueError``.  Only allowed rows are shortlisted and scored (the cut to ``shortlist`` is made among them, so a narrow filter loses
+        nothing), and a removed row (``remove``) is never allowed.  ``k`` is still checked against ``shortlist`` / ``len(index)``, not
+        against the filter, which lives on the device: a query with fewer than ``k`` allowed rows ends in ids -1 with scores -inf, and the
+        ``ground`` / ``moments`` dicts carry for those what they document for an id outside the index.  With ``allow=None`` and nothing
+        removed every launch and result is what it was."""
         k, S, chunk = self._search_checks(k, shortlist, chunk)
         if ground:
             self._ground_checks(frames)
         win = self._moment_checks(frames, moments, moment_stride) if moments is not None else None
         ids_in = text["input_ids"]
+        mask = self._filter(allow, ids_in.shape[0])
         if not ids_in.is_cuda:
             raise DemoVLPHipError("VideoIndex.search runs on an MI355X device only (no CPU fallback): move the queries to cuda")
         was_training = model.training
@@ -394,9 +549,11 @@ class VideoIndex(_ResidentIndex):
                 for q0 in range(0, ids_in.shape[0], QUERY_BLOCK):
                     block = {name: t[q0:q0 + QUERY_BLOCK] for name, t in text.items() if isinstance(t, torch.Tensor)}
                     side = self._text_side(model, block)
-                    _, ids, cos, local = self._score(model, loss_fn, block, S, chunk, side)
+                    _, ids, cos, local = self._score(model, loss_fn, block, S, chunk, side, **self._mask_arg(mask, q0, q0 + QUERY_BLOCK))
                     val, pos = ops.topk_rows(cos + local, k)
                     top = torch.gather(ids, 1, pos.long()).long()
+                    if mask is not None:
+                        val = _holes(top, val)
                     res.append((top, val, self._ground_block(loss_fn, side, block["attention_mask"], top, frames) if ground else None,
                                 self._moments_block(loss_fn, side, top, frames, win, moment_stride) if win is not None else None))
         finally:
@@ -467,11 +624,8 @@ class CaptionIndex(_ResidentIndex):
             self.local = torch.zeros((self.capacity, self.W, 256), device=dev, dtype=self.dtype)
 
     # ---- filling ------------------------------------------------------------------------------------------------------
-    def add(self, global_text, local_text, attention_mask):
-        """Append captions from the text tower's outputs (``model.compute_text``): ``global_text`` [n, 256], ``local_text`` [n, W, 256] and
-        the tokeniser's ``attention_mask`` [n, W + 1] (CLS position first).  Exactly ``W`` words: another width raises ``ValueError`` -- the
-        text tower's bf16 output depends on the shape it ran at, so padding here would break bit-equality with the full grid.  Returns the
-        index rows they took."""
+    def _checked(self, global_text, local_text, attention_mask, rows=None):
+        """the tensors of an ``add`` / ``replace`` (``rows``) call, checked -> (global, local, attention mask, n); allocates the device memory"""
         gt, lt, att = global_text, local_text, attention_mask
         n = gt.shape[0]
         if lt.dim() != 3 or lt.shape[1] != self.W or lt.shape[2] != 256:
@@ -480,21 +634,49 @@ class CaptionIndex(_ResidentIndex):
             raise ValueError(f"expected [n, 256], [n, {self.W}, 256], [n, {self.W + 1}], got {tuple(gt.shape)}, {tuple(lt.shape)}, {tuple(att.shape)}")
         if lt.dtype != self.dtype:
             raise ValueError(f"this index holds {self.dtype} embeddings, got {lt.dtype}")
-        if self.n + n > self.capacity:
+        if rows is None and self.n + n > self.capacity:
             raise ValueError(f"adding {n} captions to {self.n} exceeds the capacity {self.capacity}")
+        if rows is not None and len(rows) != n:
+            raise ValueError(f"replace: {len(rows)} rows for {n} captions")
         if not (gt.is_cuda and lt.is_cuda and att.is_cuda):
             raise DemoVLPHipError("CaptionIndex lives on an MI355X device only (no CPU fallback): embeddings must be on the device")
         self._alloc()
+        return gt, lt, att, n
+
+    def _write(self, r0, gt, lt, att):
+        n = gt.shape[0]
+        self.gn[r0:r0 + n] = ops.rownorm_fwd(gt.detach().contiguous())[0]
+        self.tm[r0:r0 + n] = ((att[:, 1:].contiguous() - 1.0) * 100.0).float()      # as trainer.evaluate (trainer/trainer_dist.py:156-159)
+        if self.fused:
+            ops.xattn_caption_index_add(self.local, self.capacity, self.W, r0, lt.detach().contiguous())
+        else:
+            self.local[r0:r0 + n] = lt.detach()
+
+    def add(self, global_text, local_text, attention_mask):
+        """Append captions from the text tower's outputs (``model.compute_text``): ``global_text`` [n, 256], ``local_text`` [n, W, 256] and
+        the tokeniser's ``attention_mask`` [n, W + 1] (CLS position first).  Exactly ``W`` words: another width raises ``ValueError`` -- the
+        text tower's bf16 output depends on the shape it ran at, so padding here would break bit-equality with the full grid.  Returns the
+        index rows they took."""
+        gt, lt, att, n = self._checked(global_text, local_text, attention_mask)
         r0 = self.n
         with torch.no_grad():
-            self.gn[r0:r0 + n] = ops.rownorm_fwd(gt.detach().contiguous())[0]
-            self.tm[r0:r0 + n] = ((att[:, 1:].contiguous() - 1.0) * 100.0).float()      # as trainer.evaluate (trainer/trainer_dist.py:156-159)
-            if self.fused:
-                ops.xattn_caption_index_add(self.local, self.capacity, self.W, r0, lt.detach().contiguous())
-            else:
-                self.local[r0:r0 + n] = lt.detach()
+            self._write(r0, gt, lt, att)
         self.n += n
         return range(r0, r0 + n)
+
+    def replace(self, rows, global_text, local_text, attention_mask):
+        """Overwrite the index rows ``rows`` (ints in [0, len(index)), one per caption; the three tensors ``add`` takes) in place: a
+        re-worded caption, or a new one in a slot ``removed()`` lists.  The rows are written by the entry ``add`` uses
+        (``dvlp_xattn_caption_index_add`` at ``row0 = r``), so a replaced row's bytes are those of a fresh index holding the same caption;
+        a removed row is live again.  Returns ``self``."""
+        rows = self._row_list(rows, "replace")
+        gt, lt, att, _ = self._checked(global_text, local_text, attention_mask, rows)
+        with torch.no_grad():
+            for i, r in enumerate(rows):
+                self._write(r, gt[i:i + 1], lt[i:i + 1], att[i:i + 1])
+            if rows:
+                self._set_alive(rows, True)
+        return self
 
     def add_batches(self, model, batches):
         """Run the text tower only (``model.compute_text``) on every batch (``{'text': {'input_ids', 'attention_mask'}, ...}`` or the text
@@ -519,6 +701,8 @@ class CaptionIndex(_ResidentIndex):
                      gn=self.gn.cpu(), tm=self.tm.cpu(), local=self.local.cpu())
         if self.tiled:      # (only tiled indexes write the key: every other state dict is what it was)
             state["tiled"] = True
+        if self.alive is not None:      # (the same pattern: written once something has been removed)
+            state["alive"] = self.alive.cpu()
         return state
 
     def load_state_dict(self, state):
@@ -530,20 +714,23 @@ class CaptionIndex(_ResidentIndex):
         for name in ("gn", "tm", "local"):
             getattr(self, name).copy_(state[name])
         self.n = int(state["n"])
+        self.alive = state["alive"].to(self.gn.device) if "alive" in state else None
         return self
 
     # ---- search -------------------------------------------------------------------------------------------------------
-    def shortlist_by_cosine(self, global_object_embeddings, shortlist, chunk=65536):
+    def shortlist_by_cosine(self, global_object_embeddings, shortlist, chunk=65536, allow=None):
         """The global stage alone: (ids int64 [Nv, S] ascending per row, cosines fp32 [Nv, S]) of the ``shortlist`` best captions per video
-        embedding [Nv, 256] by cosine (ties by smaller id)."""
+        embedding [Nv, 256] by cosine (ties by smaller id).  ``allow`` (bool [len(index)] or [Nv, len(index)] on the device; ``ValueError``
+        otherwise): only allowed rows, and never a removed one; a video with fewer than S of them starts with ids -1 (cosine -inf)."""
+        mask = self._filter(allow, global_object_embeddings.shape[0])
         if not global_object_embeddings.is_cuda or self.n == 0:
             raise DemoVLPHipError("shortlist_by_cosine needs a filled index and embeddings on an MI355X device")
         with torch.no_grad():
             ids, cos = self._global_stage(ops.rownorm_fwd(global_object_embeddings.detach().contiguous())[0], self._shortlist_size(shortlist),
-                                          int(chunk))
+                                          int(chunk), mask)
         return ids.long(), cos
 
-    def _local_stage(self, local_loss, lo, om, ids):
+    def _local_stage(self, local_loss, lo, om, ids, holes=False):
         lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
         if self.tiled:
             return Fn.XattnLongCaptionIndexPairsFn.apply(self.local, self.capacity, self.W, self.tm, lo, om, ids, lam, gate)
@@ -552,6 +739,13 @@ class CaptionIndex(_ResidentIndex):
         out = torch.empty(ids.shape, device=ids.device, dtype=torch.float32)
         for i in range(ids.shape[0]):                              # parity route: the video's captions gathered, multi-kernel grid [1, S]
             rows = ids[i].long()
+            if holes:                                              # a filtered search: the -1s of the video are dropped before the gather, NaN in their place
+                keep = rows >= 0
+                out[i] = float("nan")
+                if bool(keep.any()):
+                    rows = rows[keep]
+                    out[i, keep] = local_loss.get_sim(lo[i:i + 1], self.local[rows], om[i:i + 1], None, self.tm[rows])[0]
+                continue
             out[i] = local_loss.get_sim(lo[i:i + 1], self.local[rows], om[i:i + 1], None, self.tm[rows])[0]
         return out
 
@@ -568,13 +762,14 @@ class CaptionIndex(_ResidentIndex):
                                   "(G <= 288 and 160 KB of LDS per pair)")
         return go, lo.contiguous(), add_mask[:, 1:, ...].float().contiguous()
 
-    def _score(self, model, loss_fn, data, S, chunk, side=None):
-        """One block of query videos through the object tower (or its outputs ``side``) and both stages -> (qn, ids int32 [Nv, S], cos, local)."""
+    def _score(self, model, loss_fn, data, S, chunk, side=None, mask=None):
+        """One block of query videos through the object tower (or its outputs ``side``) and both stages -> (qn, ids int32 [Nv, S], cos, local);
+        ``mask``: the block's rows of ``_filter``."""
         local_loss = getattr(loss_fn, "local_loss", loss_fn)
         go, lo, om = side if side is not None else self._video_side(model, data)
         qn = ops.rownorm_fwd(go.contiguous())[0]
-        ids, cos = self._global_stage(qn, S, chunk)
-        return qn, ids, cos, self._local_stage(local_loss, lo, om, ids)
+        ids, cos = self._global_stage(qn, S, chunk, mask)
+        return qn, ids, cos, self._local_stage(local_loss, lo, om, ids, mask is not None)
 
     def _ground_block(self, loss_fn, side, ids, frames):
         """Grounding of one block's pairs (video i, index row ids[i, p]) from its object-tower outputs."""
@@ -623,7 +818,7 @@ class CaptionIndex(_ResidentIndex):
         try:
             with torch.no_grad():
                 for v0, block in self._blocks(data):
-                    res.append(self._ground_block(loss_fn, self._video_side(model, block), ids[v0:v0 + VIDEO_BLOCK], frames))
+                    res.append(self._ground_block(loss_fn, self._video_side(model, block), self._live_ids(ids[v0:v0 + VIDEO_BLOCK]), frames))
         finally:
             if was_training:
                 model.train()
@@ -680,13 +875,14 @@ class CaptionIndex(_ResidentIndex):
         try:
             with torch.no_grad():
                 for v0, block in self._blocks(data):
-                    res.append(self._moments_block(loss_fn, self._video_side(model, block), ids[v0:v0 + VIDEO_BLOCK], frames, win, stride))
+                    res.append(self._moments_block(loss_fn, self._video_side(model, block), self._live_ids(ids[v0:v0 + VIDEO_BLOCK]), frames, win,
+                                                   stride))
         finally:
             if was_training:
                 model.train()
         return _cat_moments(res)
 
-    def timeline(self, model, loss_fn, data, frames, windows, stride=1, k=5, shortlist=100, chunk=65536):
+    def timeline(self, model, loss_fn, data, frames, windows, stride=1, k=5, shortlist=100, chunk=65536, allow=None):
         """WHICH captions apply WHEN: for every window of ``windows`` (as in ``moments``) of every query video of ``data``, the ``k`` best
         captions of the video's cosine shortlist (``shortlist`` captions chosen by the whole video's cosine, at most 1024; ``None`` or
         ``>= len(index)``: every caption), ranked by the window's local similarity alone -- the whole-video cosine does not depend on the
@@ -695,10 +891,13 @@ class CaptionIndex(_ResidentIndex):
         ``scores`` fp32 [Nv, M_total, k], ``cosine`` fp32 [Nv, M_total, k] (the shortlist cosine of each returned caption, for a caller
         who wants to add a prior) and ``start`` / ``length`` int64 [M_total] (``moment_windows``).  Best first; equal scores go to the
         smaller index row.  A window without an unmasked region gives ``scores`` = -inf, ``ids`` = -1 and ``cosine`` = NaN.  The checks on
-        ``k``, ``shortlist`` and ``chunk`` are those of ``search``.  ``tiled=True`` indexes only; no gradient flows."""
+        ``k``, ``shortlist`` and ``chunk`` are those of ``search``.  ``tiled=True`` indexes only; no gradient flows.  ``allow`` as in
+        ``search`` (bool [len(index)] or [Nv, len(index)] on the device): no disallowed or removed caption is listed; a window of a video
+        with fewer than ``k`` allowed captions ends like an empty one (``ids`` = -1, ``scores`` = -inf, ``cosine`` = NaN)."""
         k, S, chunk = self._search_checks(k, shortlist, chunk)
         obj = data["object"]
         starts, lengths, wins = self._moment_checks(frames, windows, stride, int(obj.shape[1] * obj.shape[2]))
+        mask = self._filter(allow, obj.shape[0])
         if not obj.is_cuda:
             raise DemoVLPHipError("CaptionIndex.timeline runs on an MI355X device only (no CPU fallback): move the videos to cuda")
         was_training = model.training
@@ -706,15 +905,18 @@ class CaptionIndex(_ResidentIndex):
         res = []
         try:
             with torch.no_grad():
-                for _, block in self._blocks(data):
+                for v0, block in self._blocks(data):
                     side = self._video_side(model, block)
-                    ids, cos = self._global_stage(ops.rownorm_fwd(side[0].contiguous())[0], S, chunk)          # ids ascending per row
+                    ids, cos = self._global_stage(ops.rownorm_fwd(side[0].contiguous())[0], S, chunk,          # ids ascending per row
+                                                  self._rows_of(mask, v0, v0 + VIDEO_BLOCK))
                     scores = self._window_scores(loss_fn, side, ids, frames, wins, stride, True)                # [Nv, M_total, S]
                     Nv, M = scores.shape[:2]
                     val, pos = ops.topk_rows(scores.view(Nv * M, S), k)
                     val, pos = val.view(Nv, M, k), pos.view(Nv, M, k).long().clamp(min=0)
-                    empty = torch.isneginf(val)
                     top = torch.gather(ids.long()[:, None, :].expand(Nv, M, S), 2, pos)
+                    if mask is not None:                           # a hole of the shortlist (NaN in every window, sorted last)
+                        val = _holes(top, val)
+                    empty = torch.isneginf(val)
                     prior = torch.gather(cos[:, None, :].expand(Nv, M, S), 2, pos)
                     res.append((torch.where(empty, torch.full_like(top, -1), top), val,
                                 torch.where(empty, torch.full_like(prior, float("nan")), prior)))
@@ -724,7 +926,7 @@ class CaptionIndex(_ResidentIndex):
         return dict(ids=torch.cat([r[0] for r in res]), scores=torch.cat([r[1] for r in res]), cosine=torch.cat([r[2] for r in res]),
                     start=starts.to(obj.device), length=lengths.to(obj.device))
 
-    def search(self, model, loss_fn, data, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1):
+    def search(self, model, loss_fn, data, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1, allow=None):
         """The ``k`` best captions for every video of ``data`` (``{'object', 'object_mask'}`` on the device) ->
         ``(ids int64 [Nv, k], scores fp32 [Nv, k])`` on the device, best first, equal scores by smaller id; ids are index rows.
         With ``ground=True``: ``(ids, scores, grounding)``, the dict of ``CaptionIndex.ground`` for the k winners (one more launch over them,
@@ -737,9 +939,15 @@ class CaptionIndex(_ResidentIndex):
         ``chunk``: index rows per global-stage product.  The score is ``cos(video_i, text_j) + local(video_i, caption_j)``, the pair score of
         ``VideoIndex.search``: an exact search here is the transpose of an exact search there.  In ``trainer.evaluate``'s terms it is
         ``global_sims.T + local_sims``, NOT the transpose of its ``o2t_sims`` (which keeps the reference's transposed-addend quirk), so
-        metrics of search results are not comparable with the reference's evaluation numbers.  No gradient flows."""
+        metrics of search results are not comparable with the reference's evaluation numbers.  No gradient flows.
+
+        ``allow``: a filter, bool on the device, [len(index)] (every video) or [Nv, len(index)] (per video); anything else is a
+        ``ValueError``.  Semantics of ``VideoIndex.search``: the shortlist is cut among the allowed rows, a removed row is never allowed,
+        ``k`` is checked against ``shortlist`` / ``len(index)`` and not against the filter, and a video with fewer than ``k`` allowed
+        captions ends in ids -1 with scores -inf."""
         k, S, chunk = self._search_checks(k, shortlist, chunk)
         obj = data["object"]
+        mask = self._filter(allow, obj.shape[0])
         if ground:
             self._ground_checks(frames, int(obj.shape[1] * obj.shape[2]))
         win = self._moment_checks(frames, moments, moment_stride, int(obj.shape[1] * obj.shape[2])) if moments is not None else None
@@ -750,11 +958,13 @@ class CaptionIndex(_ResidentIndex):
         res = []
         try:
             with torch.no_grad():
-                for _, block in self._blocks(data):
+                for v0, block in self._blocks(data):
                     side = self._video_side(model, block)
-                    _, ids, cos, local = self._score(model, loss_fn, block, S, chunk, side)
+                    _, ids, cos, local = self._score(model, loss_fn, block, S, chunk, side, **self._mask_arg(mask, v0, v0 + VIDEO_BLOCK))
                     val, pos = ops.topk_rows(cos + local, k)
                     top = torch.gather(ids, 1, pos.long()).long()
+                    if mask is not None:
+                        val = _holes(top, val)
                     res.append((top, val, self._ground_block(loss_fn, side, top, frames) if ground else None,
                                 self._moments_block(loss_fn, side, top, frames, win, moment_stride) if win is not None else None))
         finally:

@@ -382,6 +382,22 @@ int dvlp_xattn_long_caption_index_moments_fwd(int64_t capacity, int64_t W, const
 int64_t dvlp_topk_workspace_bytes(int64_t M, int64_t N, int K);
 int dvlp_topk_rows(int64_t M, int64_t N, const float* x, int64_t ld, int K, int64_t index_base, float* val, int* idx, int merge,
                    void* workspace, void* stream);
+/* dvlp_topk_rows with a per-column allow mask: by definition dvlp_topk_rows applied to each row with its disallowed columns DELETED -- the
+   same total order, the same raw value bits, the same (-inf, -1) tail when fewer than K columns are allowed (a row with none is all tail); an
+   allowed column holding -inf is listed with its index, a disallowed column never is, whatever it holds.
+     allow     device memory of 32-bit words, addressed by GLOBAL column number: column c of row m takes part iff bit (index_base + c) & 31 of
+               allow[m * allow_ld + ((index_base + c) >> 5)] is set, so a caller streaming over column chunks passes the same mask with a moving
+               index_base (any value, not only multiples of 32).
+     allow_ld  words between the mask rows of consecutive matrix rows; 0 = one mask row shared by all M rows; otherwise at least
+               ceil((index_base + N) / 32).
+   Words the kernel may load: of each mask row, words index_base >> 5 .. (index_base + N - 1) >> 5, nothing before or after; in the last of
+   them the bits at or beyond index_base + N are never read as columns.  merge = 1 as above: the entries already in val / idx take part
+   unconditionally (they passed the mask when they were selected), so chunked calls equal the one-shot call bit for bit.  The scan is the
+   kernel of dvlp_topk_rows with the mask as a template parameter (one or two more word loads per 16-byte load); dvlp_topk_rows itself runs the
+   unmasked instantiation.  Shape limits, workspace and error codes of dvlp_topk_rows; DVLP_ERR_SHAPE also for a null or misaligned allow, a
+   negative allow_ld and a positive one below ceil((index_base + N) / 32).  No float atomics; the result does not depend on scheduling. */
+int dvlp_topk_rows_masked(int64_t M, int64_t N, const float* x, int64_t ld, int K, int64_t index_base, const uint32_t* allow, int64_t allow_ld,
+                          float* val, int* idx, int merge, void* workspace, void* stream);
 
 /* ---- loss heads: sim_matrix (model/model.py:582-590) + NormSoftmaxLoss (model/loss.py:126-138) + RWALoss tail
  *      (model/loss.py:105-116) + GlobalLocalLoss sum (:29-45); forward and analytic gradients in one launch        ---- */
