@@ -1147,6 +1147,62 @@ def topk_rows_masked(x, K, allow, N=None, index_base=0, out=None, merge=False):
     return val, idx
 
 
+MOMENT_MAX_T, MOMENT_MAX_M = 32, 4096      # dvlp_moment_select: 1 <= T <= 32, 1 <= M <= 4096
+
+
+def _moment_windows_arg(t, name, M, device):
+    """start / length of ``moment_select`` -> int32 [M] on ``device``: a CPU int tensor is checked and uploaded, a device int32 one trusted"""
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1:
+        raise ValueError(f"moment_select: {name} must be an int tensor [M = {M}], got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if t.shape[0] != M:
+        raise ValueError(f"moment_select: {name} holds {t.shape[0]} windows, the scores have M = {M}")
+    if t.is_cuda:
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f"moment_select: a device {name} must be contiguous int32 (it is read as it is), got {t.dtype}")
+        return t
+    low = 0 if name == "start" else 1
+    if int(t.min()) < low or int(t.max()) >= 1 << 29:
+        raise ValueError(f"moment_select: every {name} must lie in [{low}, 2^29), got {int(t.min())} .. {int(t.max())}")
+    return t.to(device=device, dtype=torch.int32)
+
+
+def moment_select(scores, start, length, T, iou, M=None):
+    """Greedy temporal non-maximum suppression per row (``dvlp_moment_select``).  ``scores`` fp32 [..., ld] on the device (leading
+    dimensions are flattened; the first ``M`` columns, default all, are the window scores of one pair), ``start`` / ``length`` int [M] in
+    frames (CPU int tensors are validated -- start >= 0, length >= 1, size M -- and uploaded; device int32 tensors are trusted) ->
+    ``(val fp32 [..., T], pos int32 [..., T])``: per row up to ``T`` windows, best first in the order of ``topk_rows`` (ties by smaller
+    position), none of which overlaps an earlier one by more than ``iou`` (``float(inter) > float(union) * iou`` suppresses); windows scoring
+    NaN or -inf are never selected, and the tail is ``pos = -1`` with ``val`` = NaN if the row holds a NaN, -inf otherwise.
+    ``iou = 1`` is plain top-T, ``iou = 0`` suppresses on any overlap.  1 <= T <= 32, 1 <= M <= 4096, 0 <= iou <= 1."""
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.dim() < 1 or scores.shape[-1] < 1:
+        raise _lib.DemoVLPHipError(f"moment_select expects fp32 scores [..., ld], got {getattr(scores, 'dtype', type(scores))} "
+                                   f"{tuple(getattr(scores, 'shape', ()))}")
+    T, iou, ld = int(T), float(iou), scores.shape[-1]
+    M = ld if M is None else int(M)
+    if M < 1 or M > ld:
+        raise ValueError(f"moment_select: M = {M} must lie in [1, ld = {ld}]")
+    if M > MOMENT_MAX_M:
+        raise ValueError(f"moment_select: M = {M} windows per row exceed the limit {MOMENT_MAX_M} (dvlp_moment_select)")
+    if T < 1 or T > MOMENT_MAX_T:
+        raise ValueError(f"moment_select: T = {T} must lie in [1, {MOMENT_MAX_T}] (dvlp_moment_select)")
+    if not 0.0 <= iou <= 1.0:
+        raise ValueError(f"moment_select: iou = {iou} must lie in [0, 1]")
+    start, length = _moment_windows_arg(start, "start", M, scores.device), _moment_windows_arg(length, "length", M, scores.device)
+    lead = tuple(scores.shape[:-1])
+    x = scores.reshape(-1, ld)
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) != ld):
+        x = x.contiguous()
+    P = x.shape[0]
+    if P * max(ld, T) >= 1 << 31:
+        raise ValueError(f"moment_select: P max(ld, T) = {P * max(ld, T)} must stay below 2^31")
+    require_gpu(x, start, length)
+    val = torch.empty((P, T), device=x.device, dtype=torch.float32)
+    pos = torch.empty((P, T), device=x.device, dtype=torch.int32)
+    if P:
+        call("dvlp_moment_select", P, M, p(x), ld, p(start), p(length), T, iou, p(val), p(pos), stream())
+    return val.view(lead + (T,)), pos.view(lead + (T,))
+
+
 def global_local_loss(gt, go, xs, temperature, lam, use_global, use_local, stages, sim=None, dsim=None):
     """Raw call of the fused loss-head kernel.  Returns dict with whichever of sim/dsim/dgt/dgo/dxs/losses were produced."""
     ref = gt if gt is not None else (xs if xs is not None else sim)

@@ -47,6 +47,14 @@ workgroup stages its caption once and walks the windows of its pair.  ``CaptionI
 video the ``k`` best captions of the video's shortlist by that window's local similarity (the kernel's window-major output, one
 ``dvlp_topk_rows`` over all windows) -- which captions apply when.
 
+Moment retrieval.  The second best window of a pair is almost always the best one shifted by a frame, so ranking windows
+needs a selection that knows they overlap in time: ``dvlp_moment_select``, greedy temporal non-maximum suppression per pair on the device
+(best first in the order of ``dvlp_topk_rows``; a pick kills every window whose intersection over union with it exceeds ``iou``).
+``moments(..., top=m, iou=0.5)`` / ``search(..., moment_top=m)`` report up to ``m`` such windows per result -- a second occurrence in the
+same video -- and ``VideoIndex.search_moments`` answers "where, in which video, does this happen": every window of every shortlisted
+video is scored, up to ``per_video`` windows per video survive the suppression, and the hits ``cos(text, video) + local(window)`` of all
+videos are ranked together, so a long video with one matching window is not diluted by its other frames.
+
 fp32 models, and region counts beyond the fused kernel's range (G > 288) without ``tiled=True``, take the parity route: the raw local
 embeddings are kept and each query's shortlist is gathered and scored by the multi-kernel ``RWALoss.get_sim`` -- slow and exact, as fp32 is
 everywhere in this package.
@@ -232,6 +240,25 @@ def _unpack_bits(words, n):
 def _holes(top, val):
     """the final cut of a filtered search: a hole (id -1, NaN score, sorted last) reads (-1, -inf)"""
     return torch.where(top < 0, torch.full_like(val, float("-inf")), val)
+
+
+def _top_arg(top, iou):
+    """the ``top`` / ``iou`` keywords of ``_moments_block``; no keyword at all without ``top``: that call is what it was"""
+    return {} if top is None else {"top": top, "iou": iou}
+
+
+def _select_checks(tiled, top, iou, M_total, what):
+    """-> (top, iou) of a moment selection (``dvlp_moment_select``), or the ValueError that names the number outside its limits"""
+    if not tiled:
+        raise ValueError(f"{what} selects among the windows of a bf16 index built with tiled=True: this index is not tiled")
+    top, iou = int(top), float(iou)
+    if top < 1 or top > ops.MOMENT_MAX_T:
+        raise ValueError(f"{what} = {top} must lie in [1, {ops.MOMENT_MAX_T}] (dvlp_moment_select)")
+    if not 0.0 <= iou <= 1.0:
+        raise ValueError(f"iou = {iou} must lie in [0, 1]")
+    if M_total > ops.MOMENT_MAX_M:
+        raise ValueError(f"{M_total} windows per pair exceed the {ops.MOMENT_MAX_M} dvlp_moment_select takes: fewer window lengths or a larger stride")
+    return top, iou
 
 
 class VideoIndex(_ResidentIndex):
@@ -470,19 +497,23 @@ class VideoIndex(_ResidentIndex):
         starts, lengths = moment_windows(frames, windows, stride)
         return starts, lengths, [int(windows)] if isinstance(windows, (int, np.integer)) else [int(w) for w in windows]
 
-    def _moments_block(self, loss_fn, side, ids, frames, windows, stride):
-        """Moments of one block's pairs (query j, index row ids[j, p]) from its text-tower outputs: one launch per window length, then the
-        best window per pair by ``dvlp_topk_rows`` (ties: the smaller position -- the earlier length, then the earlier start)."""
+    def _window_scores(self, loss_fn, side, ids, frames, wins, stride):
+        """one launch per window length over all windows of the pairs (query j, index row ids[j, p]), concatenated along the window axis"""
         local_loss = getattr(loss_fn, "local_loss", loss_fn)
         _, lt, text_mask = side
-        starts, lengths, wins = windows
         lam, gate = float(local_loss.lambda_softmax), local_loss.focal_type == "equal"
         cand = ids.to(torch.int32).contiguous()
-        scores = torch.cat([ops.xattn_long_index_moments_fwd(self.local, self.capacity, self.G, self.om, lt, text_mask, cand, int(frames), w,
-                                                             int(stride), lam, gate) for w in wins], dim=2)
-        return _best_moments(scores, starts, lengths)
+        return torch.cat([ops.xattn_long_index_moments_fwd(self.local, self.capacity, self.G, self.om, lt, text_mask, cand, int(frames), w,
+                                                           int(stride), lam, gate) for w in wins], dim=2)
 
-    def moments(self, model, loss_fn, text, ids, frames, windows, stride=1):
+    def _moments_block(self, loss_fn, side, ids, frames, windows, stride, top=None, iou=0.5):
+        """Moments of one block's pairs (query j, index row ids[j, p]) from its text-tower outputs: one launch per window length, then the
+        best window per pair by ``dvlp_topk_rows`` (ties: the smaller position -- the earlier length, then the earlier start) and, with
+        ``top``, that many non-overlapping ones by ``dvlp_moment_select``."""
+        starts, lengths, wins = windows
+        return _best_moments(self._window_scores(loss_fn, side, ids, frames, wins, stride), starts, lengths, top, iou)
+
+    def moments(self, model, loss_fn, text, ids, frames, windows, stride=1, top=None, iou=0.5):
         """WHEN (query j, index row ``ids[j, p]``) matched: every window of ``windows`` (a length or a sequence of lengths, in frames) at
         starts 0, ``stride``, ... of a video of ``frames`` frames (a divisor of G: regions are frame-major) scored as a video of its own --
         the local similarity of its regions alone; the global cosine, which does not depend on the window, is not added.  ``ids`` int
@@ -490,8 +521,19 @@ class VideoIndex(_ResidentIndex):
         an unmasked region), ``start`` / ``length`` int64 [M_total] (``moment_windows``), ``best`` int64 [Nq, k] (position of the best
         window; equal scores: the earlier length, then the earlier start) and ``best_start`` / ``best_length`` / ``best_score`` [Nq, k].
         An id outside the index gives NaN scores, NaN ``best_score`` and -1 in ``best`` / ``best_start`` / ``best_length``.  A window of
-        all ``frames`` frames scores what ``ground`` reports as ``score``, bit for bit.  ``tiled=True`` indexes only; no gradient flows."""
+        all ``frames`` frames scores what ``ground`` reports as ``score``, bit for bit.  ``tiled=True`` indexes only; no gradient flows.
+
+        ``top = m`` (1 <= m <= 32, at most 4096 windows per pair; ``ValueError`` otherwise) adds the ``m`` best windows of each pair that
+        do not overlap one another by more than ``iou`` (temporal intersection over union in frames, 0 <= iou <= 1; greedy, best first:
+        ``dvlp_moment_select``): ``top`` int64 [Nq, k, m] (positions), ``top_start`` / ``top_length`` and ``top_score``.  A
+        pair with fewer such windows ends in -1 / -1 / -1 / -inf, a hole is -1 / -1 / -1 / NaN throughout.  Column 0 equals ``best`` /
+        ``best_start`` / ``best_length`` / ``best_score`` bit for bit (but for a pair whose every window is empty: ``best`` names window 0
+        with its -inf, ``top`` selects nothing).  With ``top=None`` the dict and every launch are what they were."""
+        if top is not None and not self.tiled:
+            _select_checks(False, top, iou, 0, "top")
         win = self._moment_checks(frames, windows, stride)
+        if top is not None:
+            top, iou = _select_checks(True, top, iou, int(win[0].numel()), "top")
         ids_in = text["input_ids"]
         if not (ids_in.is_cuda and ids.is_cuda):
             raise DemoVLPHipError("VideoIndex.moments runs on an MI355X device only (no CPU fallback): move the queries and ids to cuda")
@@ -507,19 +549,21 @@ class VideoIndex(_ResidentIndex):
                 for q0 in range(0, ids_in.shape[0], QUERY_BLOCK):
                     block = {name: t[q0:q0 + QUERY_BLOCK] for name, t in text.items() if isinstance(t, torch.Tensor)}
                     res.append(self._moments_block(loss_fn, self._text_side(model, block), self._live_ids(ids[q0:q0 + QUERY_BLOCK]), frames, win,
-                                                   stride))
+                                                   stride, **_top_arg(top, iou)))
         finally:
             if was_training:
                 model.train()
         return _cat_moments(res)
 
-    def search(self, model, loss_fn, text, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1, allow=None):
+    def search(self, model, loss_fn, text, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1, allow=None,
+               moment_top=None, moment_iou=0.5):
         """The ``k`` best videos for every query of ``text`` (``{'input_ids', 'attention_mask'}`` [Nq, L] on the device) ->
         ``(ids int64 [Nq, k], scores fp32 [Nq, k])`` on the device, best first, equal scores by smaller id; ids are index rows.
         With ``ground=True``: ``(ids, scores, grounding)``, the dict of ``VideoIndex.ground`` for the k winners (one more launch over them,
         on the text-tower outputs the search used; ``frames`` as there).  With ``moments`` (window lengths in frames; needs ``frames`` and
         a ``tiled=True`` index): the dict of ``VideoIndex.moments`` for the k winners at stride ``moment_stride``, computed on the same
-        text-tower outputs, is appended as the last element of the tuple.
+        text-tower outputs, is appended as the last element of the tuple; ``moment_top`` / ``moment_iou`` are its ``top`` / ``iou`` (several
+        non-overlapping windows per winner; they need ``moments``).
 
         ``loss_fn`` supplies ``lambda_softmax`` / ``focal_type`` (a ``GlobalLocalLoss`` or its ``RWALoss``).  ``shortlist``: videos per query
         that reach the local stage, chosen by cosine (at most 1024); ``None`` or ``>= len(index)`` scores every video (exact search).
@@ -536,7 +580,13 @@ class VideoIndex(_ResidentIndex):
         k, S, chunk = self._search_checks(k, shortlist, chunk)
         if ground:
             self._ground_checks(frames)
+        if moment_top is not None and moments is None:
+            raise ValueError(f"moment_top = {moment_top} selects among the windows of moments=...: give the window lengths")
+        if moment_top is not None and not self.tiled:
+            _select_checks(False, moment_top, moment_iou, 0, "moment_top")
         win = self._moment_checks(frames, moments, moment_stride) if moments is not None else None
+        if moment_top is not None:
+            moment_top, moment_iou = _select_checks(True, moment_top, moment_iou, int(win[0].numel()), "moment_top")
         ids_in = text["input_ids"]
         mask = self._filter(allow, ids_in.shape[0])
         if not ids_in.is_cuda:
@@ -555,7 +605,8 @@ class VideoIndex(_ResidentIndex):
                     if mask is not None:
                         val = _holes(top, val)
                     res.append((top, val, self._ground_block(loss_fn, side, block["attention_mask"], top, frames) if ground else None,
-                                self._moments_block(loss_fn, side, top, frames, win, moment_stride) if win is not None else None))
+                                self._moments_block(loss_fn, side, top, frames, win, moment_stride, **_top_arg(moment_top, moment_iou))
+                                if win is not None else None))
         finally:
             if was_training:
                 model.train()
@@ -566,9 +617,71 @@ class VideoIndex(_ResidentIndex):
             out += (_cat_moments([r[3] for r in res]),)
         return out
 
+    def search_moments(self, model, loss_fn, text, k=10, frames=None, windows=(4,), stride=1, per_video=1, iou=0.5, shortlist=100, chunk=65536,
+                       allow=None):
+        """WHERE, IN WHICH VIDEO: the ``k`` best (video, window) hits for every query of ``text`` -> a dict on the device, best first:
+        ``ids`` int64 [Nq, k] (index rows), ``start`` / ``length`` int64 [Nq, k] (frames) and ``scores`` fp32 [Nq, k], the score of a hit
+        being ``cos(text, video) + local(window)``: the video's global cosine plus the local similarity of the window's regions alone.
+        ``search(..., moments=...)`` ranks videos by their whole-video score and looks for windows inside the winners only, so a long video
+        whose short window matches is diluted by its other frames and its moment is never reported; here every window of every
+        shortlisted video competes.
 
-def _best_moments(scores, starts, lengths):
-    """the moments dict of window scores [N, k, M_total]: the best window per pair by ``dvlp_topk_rows`` (K = 1; a hole's NaN row: -1 / NaN)"""
+        Per query block, all on the device and without a host synchronisation: the global stage (the ``shortlist`` best videos by cosine,
+        at most 1024; ``None`` or ``>= len(index)``: every video; ``allow`` and removed rows as in ``search``), one launch of
+        ``dvlp_xattn_long_index_moments_fwd`` per window length over ALL shortlisted videos (``frames``, ``windows``, ``stride`` as in
+        ``moments``), ``dvlp_moment_select`` with ``T = per_video`` over the [Nq S, M_total] window scores -- up to ``per_video`` hits per
+        video, none overlapping an earlier one of that video by more than ``iou`` -- the cosine added, and one
+        ``dvlp_topk_rows`` over the [Nq, S per_video] hits.  Equal scores go to the smaller index row, then to the video's better hit.
+        A query with fewer than ``k`` hits (a narrow ``allow``, removed rows, videos with fewer selectable windows than ``per_video``) ends
+        in ``ids = start = length = -1`` with score -inf.
+
+        Checked before anything is launched, each a ``ValueError`` naming the number: the rules of ``moments`` and ``search`` on ``frames``,
+        ``windows``, ``stride``, ``shortlist`` and ``chunk``; ``1 <= per_video <= 32``; ``0 <= iou <= 1``;
+        ``1 <= k <= min(1024, S per_video)``; at most 4096 windows per video.  ``tiled=True`` indexes only; no gradient flows."""
+        if not self.tiled:
+            _select_checks(False, per_video, iou, 0, "search_moments")
+        _, S, chunk = self._search_checks(1, shortlist, chunk)
+        starts, lengths, wins = self._moment_checks(frames, windows, stride)
+        M = int(starts.numel())
+        T, iou = _select_checks(True, per_video, iou, M, "per_video")
+        k = int(k)
+        if k < 1 or k > min(TOPK_MAX, S * T):
+            raise ValueError(f"k = {k} must lie in [1, min({TOPK_MAX}, shortlist x per_video = {S * T})]")
+        ids_in = text["input_ids"]
+        mask = self._filter(allow, ids_in.shape[0])
+        if not ids_in.is_cuda:
+            raise DemoVLPHipError("VideoIndex.search_moments runs on an MI355X device only (no CPU fallback): move the queries to cuda")
+        dev = ids_in.device
+        start, length = starts.to(dev), lengths.to(dev)
+        start32, length32 = start.to(torch.int32), length.to(torch.int32)
+        was_training = model.training
+        model.eval()
+        res = []
+        try:
+            with torch.no_grad():
+                for q0 in range(0, ids_in.shape[0], QUERY_BLOCK):
+                    block = {name: t[q0:q0 + QUERY_BLOCK] for name, t in text.items() if isinstance(t, torch.Tensor)}
+                    side = self._text_side(model, block)
+                    ids, cos = self._global_stage(ops.rownorm_fwd(side[0].contiguous())[0], S, chunk, self._rows_of(mask, q0, q0 + QUERY_BLOCK))
+                    Nq = ids.shape[0]
+                    val, pos = ops.moment_select(self._window_scores(loss_fn, side, ids, frames, wins, stride), start32, length32, T, iou)
+                    hit_val, hit = ops.topk_rows((val + cos[:, :, None]).view(Nq, S * T), k)      # hit: video s = hit // T, its pick hit % T
+                    hit = hit.long()
+                    window = torch.gather(pos.view(Nq, S * T).long(), 1, hit)
+                    video = torch.gather(ids.long(), 1, torch.div(hit, T, rounding_mode="floor"))
+                    none, at, minus = window < 0, window.clamp(0, M - 1), torch.full_like(window, -1)
+                    res.append((torch.where(none, minus, video), torch.where(none, minus, start[at]), torch.where(none, minus, length[at]),
+                                torch.where(none, torch.full_like(hit_val, float("-inf")), hit_val)))
+        finally:
+            if was_training:
+                model.train()
+        return dict(ids=torch.cat([r[0] for r in res]), start=torch.cat([r[1] for r in res]), length=torch.cat([r[2] for r in res]),
+                    scores=torch.cat([r[3] for r in res]))
+
+
+def _best_moments(scores, starts, lengths, top=None, iou=0.5):
+    """the moments dict of window scores [N, k, M_total]: the best window per pair by ``dvlp_topk_rows`` (K = 1; a hole's NaN row: -1 / NaN)
+    and, with ``top``, the ``top`` best that do not overlap by more than ``iou`` by ``dvlp_moment_select`` (padding: -1 / -inf; a hole: -1 / NaN)"""
     Nq, k, M = scores.shape
     val, pos = ops.topk_rows(scores.view(Nq * k, M), 1)
     val, pos = val.view(Nq, k), pos.view(Nq, k).long()
@@ -576,8 +689,14 @@ def _best_moments(scores, starts, lengths):
     start, length = starts.to(scores.device), lengths.to(scores.device)
     minus = torch.full_like(pos, -1)
     at = pos.clamp(0, M - 1)
-    return dict(scores=scores, start=start, length=length, best=torch.where(hole, minus, pos), best_start=torch.where(hole, minus, start[at]),
-                best_length=torch.where(hole, minus, length[at]), best_score=val)
+    out = dict(scores=scores, start=start, length=length, best=torch.where(hole, minus, pos), best_start=torch.where(hole, minus, start[at]),
+               best_length=torch.where(hole, minus, length[at]), best_score=val)
+    if top is not None:
+        tval, tpos = ops.moment_select(scores, start.to(torch.int32), length.to(torch.int32), top, iou)
+        tpos = tpos.long()
+        none, at, minus = tpos < 0, tpos.clamp(0, M - 1), torch.full_like(tpos, -1)
+        out.update(top=tpos, top_start=torch.where(none, minus, start[at]), top_length=torch.where(none, minus, length[at]), top_score=tval)
+    return out
 
 
 def _cat_moments(res):
@@ -845,13 +964,14 @@ class CaptionIndex(_ResidentIndex):
                                                                    int(stride), lam, gate, window_major=window_major) for w in wins],
                          dim=1 if window_major else 2)
 
-    def _moments_block(self, loss_fn, side, ids, frames, windows, stride):
+    def _moments_block(self, loss_fn, side, ids, frames, windows, stride, top=None, iou=0.5):
         """Moments of one block's pairs (video i, index row ids[i, p]) from its object-tower outputs: one launch per window length, then the
-        best window per pair by ``dvlp_topk_rows`` (ties: the smaller position -- the earlier length, then the earlier start)."""
+        best window per pair by ``dvlp_topk_rows`` (ties: the smaller position -- the earlier length, then the earlier start) and, with
+        ``top``, that many non-overlapping ones by ``dvlp_moment_select``."""
         starts, lengths, wins = windows
-        return _best_moments(self._window_scores(loss_fn, side, ids, frames, wins, stride, False), starts, lengths)
+        return _best_moments(self._window_scores(loss_fn, side, ids, frames, wins, stride, False), starts, lengths, top, iou)
 
-    def moments(self, model, loss_fn, data, ids, frames, windows, stride=1):
+    def moments(self, model, loss_fn, data, ids, frames, windows, stride=1, top=None, iou=0.5):
         """WHEN (video i, index row ``ids[i, p]``) matched: every window of ``windows`` (a length or a sequence of lengths, in frames) at
         starts 0, ``stride``, ... of the query videos of ``frames`` frames (a divisor of their G: regions are frame-major) scored as a video
         of its own against the caption -- the local similarity of its regions alone; the global cosine, which does not depend on the window,
@@ -860,9 +980,15 @@ class CaptionIndex(_ResidentIndex):
         region), ``start`` / ``length`` int64 [M_total] (``moment_windows``), ``best`` int64 [Nv, k] (position of the best window; equal
         scores: the earlier length, then the earlier start) and ``best_start`` / ``best_length`` / ``best_score`` [Nv, k].  An id outside
         the index gives NaN scores, NaN ``best_score`` and -1 in ``best`` / ``best_start`` / ``best_length``.  Each score equals, bit for
-        bit, what ``VideoIndex.moments`` gives for the same pair and window.  ``tiled=True`` indexes only; no gradient flows."""
+        bit, what ``VideoIndex.moments`` gives for the same pair and window.  ``tiled=True`` indexes only; no gradient flows.
+        ``top`` / ``iou``: as in ``VideoIndex.moments`` -- the keys ``top`` / ``top_start`` / ``top_length`` / ``top_score`` [Nv, k, top], the
+        best windows of each pair that do not overlap one another by more than ``iou`` (``dvlp_moment_select``)."""
         obj = data["object"]
+        if top is not None and not self.tiled:
+            _select_checks(False, top, iou, 0, "top")
         win = self._moment_checks(frames, windows, stride, int(obj.shape[1] * obj.shape[2]))
+        if top is not None:
+            top, iou = _select_checks(True, top, iou, int(win[0].numel()), "top")
         if ids.dim() != 2 or ids.shape[0] != obj.shape[0] or ids.dtype not in (torch.int32, torch.int64):
             raise ValueError(f"ids must be int [Nv = {obj.shape[0]}, k], got {ids.dtype} {tuple(ids.shape)}")
         if self.n == 0:
@@ -876,7 +1002,7 @@ class CaptionIndex(_ResidentIndex):
             with torch.no_grad():
                 for v0, block in self._blocks(data):
                     res.append(self._moments_block(loss_fn, self._video_side(model, block), self._live_ids(ids[v0:v0 + VIDEO_BLOCK]), frames, win,
-                                                   stride))
+                                                   stride, **_top_arg(top, iou)))
         finally:
             if was_training:
                 model.train()
@@ -926,13 +1052,15 @@ class CaptionIndex(_ResidentIndex):
         return dict(ids=torch.cat([r[0] for r in res]), scores=torch.cat([r[1] for r in res]), cosine=torch.cat([r[2] for r in res]),
                     start=starts.to(obj.device), length=lengths.to(obj.device))
 
-    def search(self, model, loss_fn, data, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1, allow=None):
+    def search(self, model, loss_fn, data, k=10, shortlist=100, chunk=65536, ground=False, frames=None, moments=None, moment_stride=1, allow=None,
+               moment_top=None, moment_iou=0.5):
         """The ``k`` best captions for every video of ``data`` (``{'object', 'object_mask'}`` on the device) ->
         ``(ids int64 [Nv, k], scores fp32 [Nv, k])`` on the device, best first, equal scores by smaller id; ids are index rows.
         With ``ground=True``: ``(ids, scores, grounding)``, the dict of ``CaptionIndex.ground`` for the k winners (one more launch over them,
         on the object-tower outputs the search used; ``frames`` as there).  With ``moments`` (window lengths in frames; needs ``frames`` and
         a ``tiled=True`` index): the dict of ``CaptionIndex.moments`` for the k winners at stride ``moment_stride``, computed on the same
-        object-tower outputs, is appended as the last element of the tuple.
+        object-tower outputs, is appended as the last element of the tuple; ``moment_top`` / ``moment_iou`` are its ``top`` / ``iou`` (they
+        need ``moments``).
 
         ``loss_fn`` supplies ``lambda_softmax`` / ``focal_type`` (a ``GlobalLocalLoss`` or its ``RWALoss``).  ``shortlist``: captions per
         video that reach the local stage, chosen by cosine (at most 1024); ``None`` or ``>= len(index)`` scores every caption (exact search).
@@ -950,7 +1078,13 @@ class CaptionIndex(_ResidentIndex):
         mask = self._filter(allow, obj.shape[0])
         if ground:
             self._ground_checks(frames, int(obj.shape[1] * obj.shape[2]))
+        if moment_top is not None and moments is None:
+            raise ValueError(f"moment_top = {moment_top} selects among the windows of moments=...: give the window lengths")
+        if moment_top is not None and not self.tiled:
+            _select_checks(False, moment_top, moment_iou, 0, "moment_top")
         win = self._moment_checks(frames, moments, moment_stride, int(obj.shape[1] * obj.shape[2])) if moments is not None else None
+        if moment_top is not None:
+            moment_top, moment_iou = _select_checks(True, moment_top, moment_iou, int(win[0].numel()), "moment_top")
         if not obj.is_cuda:
             raise DemoVLPHipError("CaptionIndex.search runs on an MI355X device only (no CPU fallback): move the videos to cuda")
         was_training = model.training
@@ -966,7 +1100,8 @@ class CaptionIndex(_ResidentIndex):
                     if mask is not None:
                         val = _holes(top, val)
                     res.append((top, val, self._ground_block(loss_fn, side, top, frames) if ground else None,
-                                self._moments_block(loss_fn, side, top, frames, win, moment_stride) if win is not None else None))
+                                self._moments_block(loss_fn, side, top, frames, win, moment_stride, **_top_arg(moment_top, moment_iou))
+                                if win is not None else None))
         finally:
             if was_training:
                 model.train()

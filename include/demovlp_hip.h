@@ -399,6 +399,22 @@ int dvlp_topk_rows(int64_t M, int64_t N, const float* x, int64_t ld, int K, int6
 int dvlp_topk_rows_masked(int64_t M, int64_t N, const float* x, int64_t ld, int K, int64_t index_base, const uint32_t* allow, int64_t allow_ld,
                           float* val, int* idx, int merge, void* workspace, void* stream);
 
+/* ---- moment selection (csrc/moments.hip; no reference counterpart) ----
+   Greedy temporal non-maximum suppression over window scores, per row.  scores is fp32 [P][ld]; the first M columns of a row are the window
+   scores of one (query, video) pair, window c covering the frames [start[c], start[c] + length[c]) (start / length int32 [M] on the device,
+   start >= 0, length >= 1, start + length < 2^30: not checked).  val is fp32 [P][T], pos int32 [P][T].  For each row independently: a window
+   is selectable while it is alive and its score is neither NaN nor -inf; T times, the selectable window that is largest in the order of
+   dvlp_topk_rows (by value, -0.0 == +0.0, then by smaller position) is written -- the bits its value had, and its position -- and killed,
+   and with it every alive window c' with  float(inter) > float(union) * iou,  where inter = max(0, min(e, e') - max(s, s')) and
+   union = len + len' - inter are integers and the right-hand side is ONE fp32 multiply.  When nothing selectable is left the remaining
+   entries are pos = -1 with val = NaN (0x7fc00000) if the row holds a NaN anywhere in its M columns, -inf otherwise.  iou = 0: any temporal
+   overlap suppresses; iou = 1: nothing but the selected window is suppressed -- dvlp_topk_rows without its NaN / -inf entries.
+   1 <= T <= 32, 1 <= M <= 4096, ld >= M, P >= 0 (0: nothing is launched), P max(ld, T) < 2^31, 0 <= iou <= 1; a null or misaligned pointer
+   or a shape violation is DVLP_ERR_SHAPE, M > 4096 or T > 32 DVLP_ERR_UNSUPPORTED, before anything is launched.  No workspace, no atomics:
+   two runs give equal bytes.  Columns [M, ld) are never read; nothing outside [P][T] of val / pos is written.  stream: a hipStream_t. */
+int dvlp_moment_select(int64_t P, int64_t M, const float* scores, int64_t ld, const int* start, const int* length, int T, float iou,
+                       float* val, int* pos, void* stream);
+
 /* ---- loss heads: sim_matrix (model/model.py:582-590) + NormSoftmaxLoss (model/loss.py:126-138) + RWALoss tail
  *      (model/loss.py:105-116) + GlobalLocalLoss sum (:29-45); forward and analytic gradients in one launch        ---- */
 int dvlp_global_local_loss(int dtype, int64_t B, int64_t d, const void* gt, const void* go, const float* xs, float temperature,
