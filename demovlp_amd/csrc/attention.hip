@@ -1824,6 +1824,7 @@ extern "C" int dvlp_attention_bwd_ex(int dtype, int mode, int64_t B, int64_t N, 
     float* const csum_dst = ext ? ext->colsum : nullptr;
     if (ext) ext->colsum_fused = 0;
     if (int rc = attn_check(a)) return rc;
+    if (dtype != DVLP_F32 && dtype != DVLP_BF16) return DVLP_ERR_DTYPE;      // (named before the missing workspace: the status says what is wrong)
     if (mode == 0 && !workspace) return DVLP_ERR_SHAPE;
     const int nseg = mode == 0 ? (int)F : 1, nk = (int)R + (mode == 0 ? 1 : 0);
     const int QC = (int)R < QC_MAX ? (int)R : QC_MAX;

@@ -19,6 +19,7 @@ ROWS = {
     "test_product_reads_no_developer_variable": "b",
     "test_bad_arguments_are_reported_not_launched": "b",
     "test_attention_and_keep_mask_entries_refuse_what_they_do_not_serve": "b A8",
+    "test_space_attention_entries_refuse_what_they_do_not_serve": "b A4",
     "test_no_reference_or_oracle_import_in_product": "b c",
     "test_gemm_plan_matches_recorded_dispatch": "b A3 A5",
     # ---- tests/test_boundary_init.py
@@ -93,6 +94,28 @@ ROWS = {
     "test_all_ones_keep_masks_equal_no_masks": "A8",
     "test_run_to_run_identical": "A8",
     "test_outputs_stay_inside_their_rows": "A8",
+    # ---- tests/test_space_attention_ref.py
+    "test_restatement_equals_the_oracle_space_attention": "A4",
+    "test_restatement_on_the_region_major_order_is_time_attention": "A4 f4",
+    "test_head_count_is_a_parameter": "A4",
+    "test_branch_helper_matches_the_dispatch_table": "A4",
+    # ---- tests/test_gpu_space_attention.py
+    "test_region_counts_vs_float64": "A4",
+    "test_region_counts_vs_float64_developer_routes": "A4",
+    "test_frame_counts_vs_float64": "A4",
+    "test_frame_counts_vs_float64_round4": "A4",
+    "test_time_attention_shapes_vs_float64": "A4 f4",
+    "test_time_attention_through_the_token_transposes": "A4 f4",
+    "test_sample_with_every_region_masked": "A4",
+    "test_sample_with_every_region_masked_developer_routes": "A4",
+    "test_head_counts_that_leave_a_partial_workgroup": "A4",
+    "test_space_attention_run_to_run_identical": "A4",
+    "test_space_attention_run_to_run_identical_developer_routes": "A4",
+    "test_separate_tensors_equal_the_packed_projection": "A4",
+    "test_separate_tensors_equal_the_packed_projection_developer_routes": "A4",
+    "test_outputs_and_workspaces_stay_inside_their_bounds": "A4",
+    "test_outputs_and_workspaces_stay_inside_their_bounds_developer_routes": "A4",
+    "test_fused_bias_gradient_column_sums": "A4 A14",
     # ---- tests/test_gpu_model.py
     "test_graft_entry_smoke_runs_and_checks_against_the_oracle": "b d",
     "test_fp32_forward_backward_vs_reference_golden": "A2 A3 A4 A5 A6 A7 A8 A9 A10 A11",

@@ -153,6 +153,42 @@ def test_attention_and_keep_mask_entries_refuse_what_they_do_not_serve(lib):
         lib.call("dvlp_dropout_attn_mask", 36, 0, 0.1, None, 0, None, None, None)
 
 
+def test_space_attention_entries_refuse_what_they_do_not_serve(lib):
+    """Space / time attention (mode 0) serves N == 1 + F*R tokens with at most 127 tokens per segment (CLS + R keys are staged together), positive
+    B, H, N, fp32 or bf16, and its backward needs a workspace.  Each is refused on the host with the documented status (null tensors: nothing
+    may be launched), by the `_ex` entries and the plain ones."""
+    def fwd(entry, ext, dtype, B, N, H, F, R):
+        tail = (None, None) if ext else (None,)                         # (ext,) stream
+        return lib.call(entry, dtype, 0, B, N, H, F, R, None, None, None, 2304, None, None, 768, 0.125, None, None, *tail)
+
+    host_ws = (ctypes.c_float * 16)()                                    # a non-null workspace: a shape refusal must not be the missing workspace's
+
+    def bwd(entry, ext, dtype, B, N, H, F, R, ws=host_ws):
+        tail = (None, None) if ext else (None,)
+        return lib.call(entry, dtype, 0, B, N, H, F, R, None, None, None, 2304, None, None, 768, None, None, None, 2304, ws, 0.125, None, 0,
+                        None, *tail)
+
+    for run, entry, ext in ((fwd, "dvlp_attention_fwd_ex", True), (bwd, "dvlp_attention_bwd_ex", True),
+                            (fwd, "dvlp_attention_fwd", False), (bwd, "dvlp_attention_bwd", False)):
+        for dtype in (lib.F32, lib.BF16):
+            for B, N, H, F, R in ((2, 1 + 3 * 17 + 1, 12, 3, 17), (2, 3 * 17, 12, 3, 17),          # N != 1 + F*R, either side
+                                  (2, 1 + 3 * 128, 12, 3, 128),                                    # R + 1 keys > 128
+                                  (0, 52, 12, 3, 17), (-1, 52, 12, 3, 17), (2, 52, 0, 3, 17), (2, 52, -12, 3, 17),
+                                  (2, 0, 12, 0, 17), (2, -50, 12, -3, 17)):                        # (N <= 0 that still equals 1 + F*R)
+                with pytest.raises(lib.DemoVLPHipError, match="bad shape"):
+                    run(entry, ext, dtype, B, N, H, F, R)
+        for dtype in (2, -1, 7):
+            with pytest.raises(lib.DemoVLPHipError, match="dtype"):
+                run(entry, ext, dtype, 2, 52, 12, 3, 17)
+    # a valid shape (the dtype cases above got past the shape check with it), no workspace: only the workspace test can refuse it
+    for entry, ext in (("dvlp_attention_bwd_ex", True), ("dvlp_attention_bwd", False)):
+        for dtype in (lib.F32, lib.BF16):
+            with pytest.raises(lib.DemoVLPHipError, match="bad shape"):
+                bwd(entry, ext, dtype, 2, 52, 12, 3, 17, ws=None)
+        with pytest.raises(lib.DemoVLPHipError, match="dtype"):                                   # the dtype is named before the missing workspace
+            bwd(entry, ext, 7, 2, 52, 12, 3, 17, ws=None)
+
+
 def test_no_reference_or_oracle_import_in_product():
     """The shipped package must never import the oracle (or /root/reference)."""
     pkg = os.path.join(ROOT, "demovlp_amd")
